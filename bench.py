@@ -9,9 +9,17 @@ loss + backward + AGC/AdamW step) of SegFormer-B0 *as the reference builds it* (
                                                        nodes release the bucketed RCCL gradient exchange on a communication
                                                        stream while the backward is still running; then the fused optimizer)
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with a `roofline` object for the dominant kernel
-(ce_dice_bwd_band_kernel; HIP-event timed on its launch stream; `roofline_gemm` = the heaviest HBM-bound GEMM launch) and a
-`cpu_baseline` object (the CPU oracle port of the reference path timed on this host's cores, bounded sample).
+Prints ONE JSON line on rank 0: the headline figure of the timed steps (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`) and the run's configuration.  A plain run does nothing else: set-up, warm-up, the timed steps, the optional
+--dump-outputs files, the line.
+
+  --dump-outputs DIR   after the timed steps, what the last one handed its caller as DIR/<name>.npy (float32; see dump_outputs)
+  --full               also the secondary figures, each measured by runs of its own after the timed steps: forward + loss + backward
+                       only, a `roofline` object for the dominant kernel (ce_dice_bwd_band_kernel; HIP-event timed on its launch
+                       stream; `roofline_gemm` = the heaviest HBM-bound GEMM launch), the input pipeline, the other BASELINE
+                       configurations / train loop / evaluate legs (tools/bench_legs.py; --no-extra-legs drops them) and a
+                       `cpu_baseline` object (the CPU oracle port of the reference path timed on this host's cores, bounded sample;
+                       --no-cpu-baseline drops it)
 """
 import argparse
 import json
@@ -82,6 +90,25 @@ def kernel_source_hash(which=None):
                 h.update(fh.read())
         out[key] = h.hexdigest()[:16]
     return out if which is None else out[which]
+
+
+DUMP_MAX_ELEMS = 7 << 20      # per dumped array (float32: 28 MiB; params + grads + loss stay under 64 MB)
+
+
+def dump_outputs(dirname, loss, params, grads):
+    """--dump-outputs: what the timed step hands its caller after the last timed step, as float32 DIR/<name>.npy -- loss.npy (the step's
+    loss), params.npy (the updated parameters) and grads.npy (the gradients the optimizer consumed), parameters concatenated in the
+    optimizer's order.  An array longer than DUMP_MAX_ELEMS is written as a fixed sample: the sorted distinct indices of
+    DUMP_MAX_ELEMS draws from numpy default_rng(0), which depend on the array's length only."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {'loss': loss.detach().float().reshape(1),
+              'params': torch.cat([t.detach().reshape(-1).float() for t in params]),
+              'grads': torch.cat([t.detach().reshape(-1).float() for t in grads])}
+    for name, t in arrays.items():
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), DUMP_MAX_ELEMS))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name + '.npy'), t.cpu().numpy())
 
 
 def cpu_baseline(sample_batch=2, timed_steps=3, loop_timed_steps=2):
@@ -177,7 +204,11 @@ def main():
     ap.add_argument('--batch', type=int, default=None, help='per-GPU batch, default 256 / 64 / 32 / 32 for cfg2 / cfg3 / cfg4 / cfg5 (BASELINE.json does not fix it; 256 x 512^2 peaks at ~44 of 288 GB; same box: 128: -2.6 %%, 192: -3 %%, 320: -1.8 %% -- '
                     'powers of two fill the tile grids; profiles/r05_batch_sweep.txt)')
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also the secondary figures (fwd+loss+bwd only, rooflines, input pipeline, extra legs, '
+                                                        'CPU baseline), each measured after the timed steps')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the last timed step\'s loss / updated parameters / gradients '
+                                                                         'as DIR/<name>.npy (float32)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--no-optimizer', action='store_true', help='time forward+loss+backward only')
     ap.add_argument('--config', default='cfg2', choices=sorted(CONFIGS),
                     help='BASELINE.json configs as the reference builds them; cfg2 = SegFormer-B0 (headline)')
@@ -186,9 +217,11 @@ def main():
                                                                  '(default: it already sits there, as the device input pipeline delivers it)')
     ap.add_argument('--fp8', action='store_true', help='cfg3 / cfg5: the UPerHead 3x3 convolutions and the ConvNeXt block MLPs on fp8 operands in all three '
                                                       'products (forward e4m3 x e4m3, gradients e5m2; set_fp8)')
-    ap.add_argument('--no-extra-legs', action='store_true', help='skip the secondary legs (other BASELINE configs, train loop, evaluate)')
+    ap.add_argument('--no-extra-legs', action='store_true', help='with --full: skip the secondary legs (other BASELINE configs, train loop, evaluate)')
     ap.add_argument('--legs-budget-s', type=float, default=210.0, help='wall-clock budget for the secondary legs; legs that do not fit are listed as skipped')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.batch is None:
         args.batch = DEFAULT_BATCH[args.config]
 
@@ -286,104 +319,105 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = tmax.item()
     final_loss = loss.item()
-    # secondary figure: forward + loss + backward only (the metric's literal wording), same session
-    for _ in range(2):
-        step(False)
-    sync()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step(False)
-    sync()
-    fb = time.perf_counter() - t1
-    # roofline leg: the same C-ABI calls on the same shapes, HIP-event timed on the launch stream right after the timed
-    # region (launches inside a graph replay cannot be bracketed by events; the rocprofv3 summary of this command under
-    # profiles/ gives the in-graph durations of the same launches)
-    lo_ = torch.randn(M, ld, device=dev).to(dtype)[:, :NC]
-    loss_, stats_, lse_ = hip.ce_dice_fwd(lo_, args.batch, NC, hq, wq, H, W, y, 255, None, True, want_lse=True)   # as the step runs it
-    go_ = torch.ones(1, device=dev)
-    A_ = torch.randn(M, K, device=dev).to(dtype)
-    W_ = torch.zeros(ld, K, device=dev, dtype=dtype)
-    b_ = torch.zeros(ld, device=dev)
-    # the classifier product as it runs INSIDE the step: segf_gemm_pro, BatchNorm + ReLU + Dropout2d applied to the operand on
-    # its way into LDS (gemm_bf16_big_kernel<0, bf16, false, PRO=true>), not the plain segf_gemm of the same shape
-    rps_ = hq * wq
-    use_pro = dtype == torch.bfloat16 and hip.gemm_pro_supported(dtype, 0, M, ld, K, rps_)
-    sc_ = torch.ones(args.batch, K, device=dev)
-    sh_ = torch.zeros(args.batch, K, device=dev)
-    with hip.KernelTimer(lambda k: k in (loss_key, gemm_key)) as kt:
-        for _ in range(max(args.steps, 5)):
-            hip.ce_dice_bwd(lo_, args.batch, NC, hq, wq, H, W, y, 255, None, True, stats_, go_, lse=lse_)
-            if use_pro:
-                hip.gemm_pro(0, A_, W_, M, ld, K, sc_, sh_, rps_, 1, bias=b_)
-            else:
-                hip.gemm(0, A_, W_, M, ld, K, bias=b_)
-    esz = A_.element_size()
-    # SURVEY 8(d), loss kernel: low-res logits read + their gradient written (NC classes, not the padded row) + int64 labels read
-    loss_bytes = args.batch * (2 * hq * wq * NC * esz + H * W * 8)
-    loss_bytes_padded = args.batch * (2 * hq * wq * ld * esz + H * W * 8)      # what the rows occupy in memory (class pad columns)
-    loss_exps = float(args.batch) * H * W * (16 * ((NC + 15) // 16)) * (8.0 / 7.0) * (17.0 / 16.0)   # per pixel and padded class; band sweep: 8 cells per 7 tap columns, one lead-in row per 16-row segment
-    gemm_bytes = esz * (M * K + ld * K + M * ld)
-    del A_, W_, lo_
+    if args.dump_outputs and rank == 0:
+        # the optimizer's per-parameter views of its flat parameter / gradient buffers (graphed and eager path alike)
+        dump_outputs(args.dump_outputs, loss, opt._params, opt._grad_views)
+    if args.full:
+        # secondary figure: forward + loss + backward only (the metric's literal wording), same session
+        for _ in range(2):
+            step(False)
+        sync()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step(False)
+        sync()
+        fb = time.perf_counter() - t1
+        # roofline leg: the same C-ABI calls on the same shapes, HIP-event timed on the launch stream right after the timed
+        # region (launches inside a graph replay cannot be bracketed by events; the rocprofv3 summary of this command under
+        # profiles/ gives the in-graph durations of the same launches)
+        lo_ = torch.randn(M, ld, device=dev).to(dtype)[:, :NC]
+        loss_, stats_, lse_ = hip.ce_dice_fwd(lo_, args.batch, NC, hq, wq, H, W, y, 255, None, True, want_lse=True)   # as the step runs it
+        go_ = torch.ones(1, device=dev)
+        A_ = torch.randn(M, K, device=dev).to(dtype)
+        W_ = torch.zeros(ld, K, device=dev, dtype=dtype)
+        b_ = torch.zeros(ld, device=dev)
+        # the classifier product as it runs INSIDE the step: segf_gemm_pro, BatchNorm + ReLU + Dropout2d applied to the operand on
+        # its way into LDS (gemm_bf16_big_kernel<0, bf16, false, PRO=true>), not the plain segf_gemm of the same shape
+        rps_ = hq * wq
+        use_pro = dtype == torch.bfloat16 and hip.gemm_pro_supported(dtype, 0, M, ld, K, rps_)
+        sc_ = torch.ones(args.batch, K, device=dev)
+        sh_ = torch.zeros(args.batch, K, device=dev)
+        with hip.KernelTimer(lambda k: k in (loss_key, gemm_key)) as kt:
+            for _ in range(max(args.steps, 5)):
+                hip.ce_dice_bwd(lo_, args.batch, NC, hq, wq, H, W, y, 255, None, True, stats_, go_, lse=lse_)
+                if use_pro:
+                    hip.gemm_pro(0, A_, W_, M, ld, K, sc_, sh_, rps_, 1, bias=b_)
+                else:
+                    hip.gemm(0, A_, W_, M, ld, K, bias=b_)
+        esz = A_.element_size()
+        # SURVEY 8(d), loss kernel: low-res logits read + their gradient written (NC classes, not the padded row) + int64 labels read
+        loss_bytes = args.batch * (2 * hq * wq * NC * esz + H * W * 8)
+        loss_bytes_padded = args.batch * (2 * hq * wq * ld * esz + H * W * 8)      # what the rows occupy in memory (class pad columns)
+        loss_exps = float(args.batch) * H * W * (16 * ((NC + 15) // 16)) * (8.0 / 7.0) * (17.0 / 16.0)   # per pixel and padded class; band sweep: 8 cells per 7 tap columns, one lead-in row per 16-row segment
+        gemm_bytes = esz * (M * K + ld * K + M * ld)
+        del A_, W_, lo_
 
-    # input-pipeline leg: one batch of the reference's train transform stack (crop, Pillow colour jitter, flip,
-    # ToTensor, Normalize, label table) from decoded uint8 images resident in HBM -- reported beside the step, not part of `value`
-    inp = None
-    if rank == 0 and H % 4 == 0:
-        import random as _random
-        from segmentation_factory_amd.transforms import DeviceTrainTransform, label_table
-        gen_ = torch.Generator(device=dev).manual_seed(0)
-        srcs_ = [(H + 40 + (k % 7) * 13, W + 60 + (k % 5) * 29) for k in range(args.batch)]
-        imgs_ = [torch.randint(0, 256, (h_, w_, 3), dtype=torch.uint8, device=dev, generator=gen_) for h_, w_ in srcs_]
-        lbls_ = [torch.randint(0, 256, (h_, w_), dtype=torch.uint8, device=dev, generator=gen_) for h_, w_ in srcs_]
-        tr_ = DeviceTrainTransform((H, W), label_lut=label_table({255: 0}, dev), device=dev, rng=_random.Random(0))
-        smp_ = tr_.pack(imgs_, lbls_, [tr_.draw(h_, w_) for h_, w_ in srcs_])
-        oi_, ol_ = hip.input_train(smp_, args.batch, H, W, tr_.mean, tr_.std, tr_.label_lut)
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-        for _ in range(10):
-            hip.input_train(smp_, args.batch, H, W, tr_.mean, tr_.std, tr_.label_lut, oi_, ol_)
-        ev1.record()
-        torch.cuda.synchronize()
-        inp_ms = ev0.elapsed_time(ev1) / 10
-        inp_bytes = args.batch * H * W * 24                      # 3 + 1 bytes read, 12 + 8 written per output pixel
-        inp = {"kernels": "input_lsum_kernel + input_train_kernel (segf_input_train)", "ms_per_batch": round(inp_ms, 4),
-               "images_per_sec": round(args.batch / inp_ms * 1e3), "algorithmic_bytes_per_batch": inp_bytes,
-               "achieved_GBps": round(inp_bytes / inp_ms / 1e6, 1), "frac_of_hbm_peak": round(inp_bytes / (inp_ms * 1e-3) / HBM_PEAK, 4),
-               "note": "bit-exact against Pillow + torch CPU (tests/test_input_pipeline.py); sources ~(H+80) x (W+120) uint8"}
-        del imgs_, lbls_, oi_, ol_
+        # input-pipeline leg: one batch of the reference's train transform stack (crop, Pillow colour jitter, flip,
+        # ToTensor, Normalize, label table) from decoded uint8 images resident in HBM -- reported beside the step, not part of `value`
+        inp = None
+        if rank == 0 and H % 4 == 0:
+            import random as _random
+            from segmentation_factory_amd.transforms import DeviceTrainTransform, label_table
+            gen_ = torch.Generator(device=dev).manual_seed(0)
+            srcs_ = [(H + 40 + (k % 7) * 13, W + 60 + (k % 5) * 29) for k in range(args.batch)]
+            imgs_ = [torch.randint(0, 256, (h_, w_, 3), dtype=torch.uint8, device=dev, generator=gen_) for h_, w_ in srcs_]
+            lbls_ = [torch.randint(0, 256, (h_, w_), dtype=torch.uint8, device=dev, generator=gen_) for h_, w_ in srcs_]
+            tr_ = DeviceTrainTransform((H, W), label_lut=label_table({255: 0}, dev), device=dev, rng=_random.Random(0))
+            smp_ = tr_.pack(imgs_, lbls_, [tr_.draw(h_, w_) for h_, w_ in srcs_])
+            oi_, ol_ = hip.input_train(smp_, args.batch, H, W, tr_.mean, tr_.std, tr_.label_lut)
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+            for _ in range(10):
+                hip.input_train(smp_, args.batch, H, W, tr_.mean, tr_.std, tr_.label_lut, oi_, ol_)
+            ev1.record()
+            torch.cuda.synchronize()
+            inp_ms = ev0.elapsed_time(ev1) / 10
+            inp_bytes = args.batch * H * W * 24                      # 3 + 1 bytes read, 12 + 8 written per output pixel
+            inp = {"kernels": "input_lsum_kernel + input_train_kernel (segf_input_train)", "ms_per_batch": round(inp_ms, 4),
+                   "images_per_sec": round(args.batch / inp_ms * 1e3), "algorithmic_bytes_per_batch": inp_bytes,
+                   "achieved_GBps": round(inp_bytes / inp_ms / 1e6, 1), "frac_of_hbm_peak": round(inp_bytes / (inp_ms * 1e-3) / HBM_PEAK, 4),
+                   "note": "bit-exact against Pillow + torch CPU (tests/test_input_pipeline.py); sources ~(H+80) x (W+120) uint8"}
+            del imgs_, lbls_, oi_, ol_
 
-    # HBM traffic per launch from the PMC counters (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of THIS command,
-    # corrected as MI355X_MICROARCH.md prescribes; committed under profiles/): reported only for the batch it was measured at
-    traffic, traffic_note = {}, {}
-    try:
-        with open(os.path.join(ROOT, 'profiles', f'pmc_traffic_b{args.batch}.json')) as fh:
-            pmc = json.load(fh)
-        have = pmc.get('source_hashes') or {}
-        now = kernel_source_hash()
-        usable = pmc.get('batch') == args.batch and args.config == 'cfg2' and args.dtype == 'bf16'
+        # HBM traffic per launch from the PMC counters (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of THIS command,
+        # FETCH_SIZE doubled: gfx950 counts a 128-B request as 64 B; committed under profiles/): reported only for the batch it was measured at
+        traffic, traffic_note = {}, {}
+        try:
+            with open(os.path.join(ROOT, 'profiles', f'pmc_traffic_b{args.batch}.json')) as fh:
+                pmc = json.load(fh)
+            have = pmc.get('source_hashes') or {}
+            now = kernel_source_hash()
+            usable = pmc.get('batch') == args.batch and args.config == 'cfg2' and args.dtype == 'bf16'
+            for key in KERNEL_SOURCES:
+                if not usable:
+                    traffic_note[key] = 'no counter file for this batch / configuration'
+                elif have.get(key) != now[key]:
+                    traffic_note[key] = (f"profiles/pmc_traffic_b{args.batch}.json was measured on other sources of this kernel "
+                                         f"(hash {have.get(key)}, now {now[key]}): not reported")
+                else:
+                    traffic_note[key] = f"rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes, kernel sources {now[key]}"
+            for kname, v in pmc['kernels'].items():
+                if kname.startswith('ce_dice_bwd') and traffic_note.get('loss_bwd', '').startswith('rocprofv3'):
+                    traffic['loss_bwd'] = max(traffic.get('loss_bwd', 0), v['total_bytes'])      # (the retry kernel shares the prefix and moves no data)
+                if kname.startswith('gemm_bf16_big_kernel<0') and traffic_note.get('gemm_pro', '').startswith('rocprofv3'):
+                    targs = [t.strip() for t in kname[kname.index('<') + 1:kname.rindex('>')].split(',')]    # layout, out type, CONV, PRO, SHAPE, DEEP
+                    if len(targs) > 3 and targs[3] == 'true':
+                        traffic['gemm_pro'] = max(traffic.get('gemm_pro', 0), v['total_bytes'])
+        except (OSError, ValueError, KeyError):
+            pass
         for key in KERNEL_SOURCES:
-            if not usable:
-                traffic_note[key] = 'no counter file for this batch / configuration'
-            elif have.get(key) != now[key]:
-                traffic_note[key] = (f"profiles/pmc_traffic_b{args.batch}.json was measured on other sources of this kernel "
-                                     f"(hash {have.get(key)}, now {now[key]}): not reported")
-            else:
-                traffic_note[key] = f"rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes, kernel sources {now[key]}"
-        for kname, v in pmc['kernels'].items():
-            if kname.startswith('ce_dice_bwd') and traffic_note.get('loss_bwd', '').startswith('rocprofv3'):
-                traffic['loss_bwd'] = max(traffic.get('loss_bwd', 0), v['total_bytes'])      # (the retry kernel shares the prefix and moves no data)
-            if kname.startswith('gemm_bf16_big_kernel<0') and traffic_note.get('gemm_pro', '').startswith('rocprofv3'):
-                targs = [t.strip() for t in kname[kname.index('<') + 1:kname.rindex('>')].split(',')]    # layout, out type, CONV, PRO, SHAPE, DEEP
-                if len(targs) > 3 and targs[3] == 'true':
-                    traffic['gemm_pro'] = max(traffic.get('gemm_pro', 0), v['total_bytes'])
-    except (OSError, ValueError, KeyError):
-        pass
-    for key in KERNEL_SOURCES:
-        traffic_note.setdefault(key, 'no counter file for this batch / configuration')
+            traffic_note.setdefault(key, 'no counter file for this batch / configuration')
     if rank == 0:
-        summ = kt.summary()
-        nl, avg_ms = summ.get(loss_key, (0, float('nan')))
-        ng, gemm_ms = summ.get(gemm_key, (0, float('nan')))
         ips = world * args.batch * args.steps / elapsed
         out = {
             "metric": "images/sec/GPU fwd+bwd SegFormer-B0 512x512 bf16; mIoU parity vs CPU ref" if args.config == 'cfg2'
@@ -403,55 +437,61 @@ def main():
                        "launch": "eager" if args.eager else "hipGraph(zero_grad+fwd+loss+bwd+grad gather) + RCCL all-reduce + fused AGC/AdamW"},
             "images_per_sec_per_gpu": round(ips / world, 2),
             "peak_hbm_allocated_gb": round(torch.cuda.max_memory_allocated() / 1e9, 1),
-            "fwd_loss_bwd_only_images_per_sec": round(world * args.batch * args.steps / fb, 2),
             "reference_graph_tflops_equivalent": round(3 * FWD_GFLOP_PER_IMG * 1e9 * ips / 1e12, 1) if args.config == 'cfg2' else None,
             # whole-step view with SURVEY section 8(d)'s algorithmic bytes (580 MB per image fwd+bwd at cfg2: every GEMM-class
             # output written once / read once per pass, bf16) -- the per-kernel rooflines below are the graded ones
             "step_algorithmic_hbm": ({"bytes_per_image": 580e6, "achieved_GBps": round(580e6 * ips / world / 1e9, 1),
                                       "frac_of_peak": round(580e6 * ips / world / HBM_PEAK, 4)} if args.config == 'cfg2' else None),
-            "roofline": {"kernel": "ce_dice_bwd_band_kernel (dominant kernel by GPU time): fused transposed upsample + softmax + CE/Dice "
-                                   f"backward, low-res logits [B,{hq},{wq},{ld}] -> d logits, labels int64 [B,{H},{W}]",
-                         "bound": "hbm", "achieved": round(loss_bytes / (avg_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                         "frac": round(loss_bytes / (avg_ms * 1e-3) / HBM_PEAK, 4), "traffic": traffic.get('loss_bwd'), "traffic_source": traffic_note['loss_bwd'],
-                         "traffic_over_algorithmic": round(traffic['loss_bwd'] / loss_bytes, 3) if traffic.get('loss_bwd') else None,
-                         "launches_timed": nl, "avg_launch_ms": round(avg_ms, 4), "algorithmic_bytes_per_launch": loss_bytes,
-                         "padded_row_bytes_per_launch": loss_bytes_padded,
-                         "note": "VALU-issue-bound, not HBM-bound: one v_exp_f32 per (full-resolution pixel, class) plus ~3.6 other VALU "
-                                 "instructions (ISA count: 149 VALU + 41 transcendental + 20 MFMA per 16-pixel cell; the softmax normalisation arrives as the "
-                                 "forward's per-pixel log-sum, +64 B per cell, not counted in the algorithmic bytes); interpolation / tap scatter on MFMA.  exp_per_second = %.3e (v_exp_f32 issue peak ~2.0e13/s)"
-                                 % (loss_exps / (avg_ms * 1e-3))},
-            "roofline_gemm": {"kernel": "gemm_bf16_big_kernel<0, bf16, false, PRO=true, SHAPE=1, DEEP=true> (segf_gemm_pro, the in-graph variant; narrow 64x80 wave tiles, three K steps of the streamed operand in flight, packed operand prologue): classifier 1x1 conv "
-                                        f"[B*{hq}*{wq},768]x[768,{ld}] with BatchNorm + ReLU + Dropout2d applied on the operand load" if use_pro else
-                                        f"gemm_bf16_big_kernel<0>: classifier 1x1 conv [B*{hq}*{wq},768]x[768,{ld}]",
-                              "bound": "hbm", "achieved": round(gemm_bytes / (gemm_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK / 1e9,
-                              "unit": "GB/s", "frac": round(gemm_bytes / (gemm_ms * 1e-3) / HBM_PEAK, 4),
-                              "traffic": traffic.get('gemm_pro'), "traffic_source": traffic_note['gemm_pro'],
-                              "traffic_over_algorithmic": round(traffic['gemm_pro'] / gemm_bytes, 3) if traffic.get('gemm_pro') else None,
-                              "launches_timed": ng,
-                              "avg_launch_ms": round(gemm_ms, 4), "algorithmic_bytes_per_launch": gemm_bytes,
-                              "flops_per_launch": 2.0 * M * ld * K},
         }
-        if args.config != 'cfg2':
-            # the loss kernel is NOT what carries these steps (cfg3 / cfg5: the UPerHead 3x3 implicit GEMMs, 68 % / 37 % of the GPU time;
-            # cfg4: head-dim-64 attention, 36 %): `roofline` prices that config's own dominant kernel, the loss kernel moves aside
-            sys.path.insert(0, os.path.join(ROOT, 'tools'))
-            from bench_legs import dominant_kernel
-            out["roofline_loss"] = out["roofline"]
-            gs = step = None
-            torch.cuda.empty_cache()
-            out["roofline"] = dominant_kernel(args.config, args.batch, NC, H, W, args.fp8)
-        if inp is not None:
-            out["input_pipeline"] = inp
-        # (never under a profiler: its preloaded library has initialised the GPU in this process, and a child process started from
-        # here is the forbidden exec-after-GPU-init)
-        profiled = 'rocprofiler' in os.environ.get('LD_PRELOAD', '') or any(k.startswith(('ROCPROF', 'ROCP_')) for k in os.environ)
-        if world == 1 and not args.no_extra_legs and not profiled and args.config == 'cfg2' and not args.eager:
-            # free this process's share of the HBM first: the children build their own models and graphs
-            gs = None
-            torch.cuda.empty_cache()
-            out.update(extra_legs(args.legs_budget_s))
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline()
+        if args.full:
+            summ = kt.summary()
+            nl, avg_ms = summ.get(loss_key, (0, float('nan')))
+            ng, gemm_ms = summ.get(gemm_key, (0, float('nan')))
+            out["fwd_loss_bwd_only_images_per_sec"] = round(world * args.batch * args.steps / fb, 2)
+            out.update({
+                "roofline": {"kernel": "ce_dice_bwd_band_kernel (dominant kernel by GPU time): fused transposed upsample + softmax + CE/Dice "
+                                       f"backward, low-res logits [B,{hq},{wq},{ld}] -> d logits, labels int64 [B,{H},{W}]",
+                             "bound": "hbm", "achieved": round(loss_bytes / (avg_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                             "frac": round(loss_bytes / (avg_ms * 1e-3) / HBM_PEAK, 4), "traffic": traffic.get('loss_bwd'), "traffic_source": traffic_note['loss_bwd'],
+                             "traffic_over_algorithmic": round(traffic['loss_bwd'] / loss_bytes, 3) if traffic.get('loss_bwd') else None,
+                             "launches_timed": nl, "avg_launch_ms": round(avg_ms, 4), "algorithmic_bytes_per_launch": loss_bytes,
+                             "padded_row_bytes_per_launch": loss_bytes_padded,
+                             "note": "VALU-issue-bound, not HBM-bound: one v_exp_f32 per (full-resolution pixel, class) plus ~3.6 other VALU "
+                                     "instructions (ISA count: 149 VALU + 41 transcendental + 20 MFMA per 16-pixel cell; the softmax normalisation arrives as the "
+                                     "forward's per-pixel log-sum, +64 B per cell, not counted in the algorithmic bytes); interpolation / tap scatter on MFMA.  exp_per_second = %.3e (v_exp_f32 issue peak ~2.0e13/s)"
+                                     % (loss_exps / (avg_ms * 1e-3))},
+                "roofline_gemm": {"kernel": "gemm_bf16_big_kernel<0, bf16, false, PRO=true, SHAPE=1, DEEP=true> (segf_gemm_pro, the in-graph variant; narrow 64x80 wave tiles, three K steps of the streamed operand in flight, packed operand prologue): classifier 1x1 conv "
+                                            f"[B*{hq}*{wq},768]x[768,{ld}] with BatchNorm + ReLU + Dropout2d applied on the operand load" if use_pro else
+                                            f"gemm_bf16_big_kernel<0>: classifier 1x1 conv [B*{hq}*{wq},768]x[768,{ld}]",
+                                  "bound": "hbm", "achieved": round(gemm_bytes / (gemm_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK / 1e9,
+                                  "unit": "GB/s", "frac": round(gemm_bytes / (gemm_ms * 1e-3) / HBM_PEAK, 4),
+                                  "traffic": traffic.get('gemm_pro'), "traffic_source": traffic_note['gemm_pro'],
+                                  "traffic_over_algorithmic": round(traffic['gemm_pro'] / gemm_bytes, 3) if traffic.get('gemm_pro') else None,
+                                  "launches_timed": ng,
+                                  "avg_launch_ms": round(gemm_ms, 4), "algorithmic_bytes_per_launch": gemm_bytes,
+                                  "flops_per_launch": 2.0 * M * ld * K},
+            })
+            if args.config != 'cfg2':
+                # the loss kernel is NOT what carries these steps (cfg3 / cfg5: the UPerHead 3x3 implicit GEMMs, 68 % / 37 % of the GPU time;
+                # cfg4: head-dim-64 attention, 36 %): `roofline` prices that config's own dominant kernel, the loss kernel moves aside
+                sys.path.insert(0, os.path.join(ROOT, 'tools'))
+                from bench_legs import dominant_kernel
+                out["roofline_loss"] = out["roofline"]
+                gs = step = None
+                torch.cuda.empty_cache()
+                out["roofline"] = dominant_kernel(args.config, args.batch, NC, H, W, args.fp8)
+            if inp is not None:
+                out["input_pipeline"] = inp
+            # (never under a profiler: its preloaded library has initialised the GPU in this process, and the legs' child processes are
+            # not started from a profiled process)
+            profiled = 'rocprofiler' in os.environ.get('LD_PRELOAD', '') or any(k.startswith(('ROCPROF', 'ROCP_')) for k in os.environ)
+            if world == 1 and not args.no_extra_legs and not profiled and args.config == 'cfg2' and not args.eager:
+                # free this process's share of the HBM first: the children build their own models and graphs
+                gs = None
+                torch.cuda.empty_cache()
+                out.update(extra_legs(args.legs_budget_s))
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

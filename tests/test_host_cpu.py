@@ -82,7 +82,9 @@ def test_metric_logger_line_format(capsys):
     out = capsys.readouterr().out.splitlines()
     # same layout as the reference's util/utils.py:190-208 line, e.g.
     # "Epoch: [0]  [0/6]  eta: 0:00:00  lr: 0.050000  loss: 3.1562 (3.1562)  time: 0.0725  data: 0.0000"
-    assert re.match(r'Epoch: \[0\]  \[0/3\]  eta: 0:00:00  lr: 0\.001000  loss: 1\.5000 \(1\.5000\)  time: \d+\.\d{4}  data: \d+\.\d{4}$', out[0])
+    # plus "  max mem: <MB>" where a GPU is visible (the reference's `if torch.cuda.is_available()` field)
+    mem = r'  max mem: \d+' if torch.cuda.is_available() else ''
+    assert re.match(r'Epoch: \[0\]  \[0/3\]  eta: 0:00:00  lr: 0\.001000  loss: 1\.5000 \(1\.5000\)  time: \d+\.\d{4}  data: \d+\.\d{4}' + mem + '$', out[0])
     assert out[-1].startswith('Epoch: [0] Total time:')
 
 

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/tab; mkdir -p $O
 for v in a b; do
   if [ $v = b ]; then export $SET; else unset ${SET%%=*}; fi
   rm -rf $O/prof_$v
-  rocprofv3 --kernel-trace --output-format csv -d $O/prof_$v -o p -- python3 $R/bench.py --config $cfg --batch $b --no-cpu-baseline --no-extra-legs --steps 4 --warmup 2 "$@" > $O/bench_$v.json 2> $O/err_$v.txt
+  rocprofv3 --kernel-trace --output-format csv -d $O/prof_$v -o p -- python3 $R/bench.py --full --config $cfg --batch $b --no-cpu-baseline --no-extra-legs --steps 4 --warmup 2 "$@" > $O/bench_$v.json 2> $O/err_$v.txt
   f=$(find $O/prof_$v -name '*kernel_trace.csv' | head -1); cp $f $O/trace_$v.csv; rm -rf $O/prof_$v
 done
 unset ${SET%%=*}
