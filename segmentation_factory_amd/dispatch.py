@@ -23,7 +23,7 @@ _PLACEHOLDER = 0x7f0000000000          # never dereferenced: dry runs skip every
 def _replayable(name):
     if name.startswith(_SKIP_PREFIX) or name in _SKIP:
         return False
-    res, args = hip._PROTOS[name]
+    res, args = hip._DECLS[name]
     return res is hip._i and all(a in (hip._i, hip._l, hip._f, hip._p) for a in args)
 
 
@@ -59,9 +59,9 @@ class _Recorder:
                 self._sink.append({'fn': name, 'args': [int(dt), desc], 'kernels': t.kernels})
                 return rc
             return grouped
-        if name not in hip._PROTOS or not _replayable(name):
+        if name not in hip._DECLS or not _replayable(name):
             return fn
-        argtypes = hip._PROTOS[name][1]
+        argtypes = hip._DECLS[name][1]
 
         def call(*args):
             with hip.trace() as t:
@@ -116,7 +116,7 @@ def replay(entry):
                 it.dy, it.x, it.dw, it.db, it.ws = (_PLACEHOLDER + 0x1000 * (5 * k + j) for j in range(5))
             rc = lib.segf_gemm_dw_db_grouped(dt, len(desc), C.cast(arr, C.c_void_p), None)
         else:
-            argtypes = hip._PROTOS[name][1]
+            argtypes = hip._DECLS[name][1]
             rc = getattr(lib, name)(*[_dec(a, v) for a, v in zip(argtypes, args)])
     if rc != 0:
         raise RuntimeError(f'{name}{tuple(args)} returned {rc} in a dry run')

@@ -7,136 +7,92 @@ raised (the reference's own error convention is Python exceptions, SURVEY.md sec
 """
 import ctypes as C
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SEGFAC_HIP_LIB: another build of the same library (same-box A/B of kernel changes, tools/ab_bench.sh); default in-tree
 LIB_PATH = os.environ.get('SEGFAC_HIP_LIB') or os.path.join(_HERE, 'libsegfac_hip.so')
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'segfac.h'))
 F32, BF16 = 0, 1
 ERR_SHAPE = -1          # SEGF_ERR_SHAPE
 _lib = None
 
+# ---- the binding is derived from include/segfac.h: its declarations are the only copy of the C ABI ----------------------------
 _i, _l, _f, _p = C.c_int, C.c_int64, C.c_float, C.c_void_p
-_PROTOS = {
-    'segf_cast': (_i, [_p, _i, _p, _i, _l, _p]),
-    'segf_cast2d': (_i, [_p, _i, _l, _p, _i, _l, _l, _l, _p]),
-    'segf_permute021': (_i, [_p, _i, _p, _i, _l, _l, _l, _l, _p]),
-    'segf_prep_grouped': (_i, [_i, _p, _p]),
-    'segf_scale_rows': (_i, [_i, _p, _l, _p, _l, _p, _l, _l, _l, _p]),
-    'segf_add': (_i, [_i, _p, _l, _p, _l, _p, _l, _l, _l, _p]),
-    'segf_colsum_ws': (_l, [_l, _l]),
-    'segf_colsum': (_i, [_i, _p, _l, _l, _l, _p, _p, _p]),
-    'segf_gemm': (_i, [_i, _i, _l, _l, _l, _p, _l, _p, _l, _p, _i, _l, _p, _p, _l, _p, _l, _i, _p, _p]),
-    'segf_gemm_pick_splitk': (_i, [_l, _l, _l]),
-    'segf_conv3x3_pick_splitk': (_i, [_i, _i, _l]),
-    'segf_conv3x3_fwd_splitk': (_i, [_i, _i, _i, _i, _i, _i]),
-    'segf_argmax_rows': (_i, [_i, _l, _i, _p, _l, _p, _p]),
-    'segf_gemm_dw_db_ws': (_l, [_l, _l, _l, _i]),
-    'segf_gemm_pro_supported': (_i, [_i, _i, _l, _l, _l, _l]),
-    'segf_gemm_pro': (_i, [_i, _i, _l, _l, _l, _p, _l, _p, _l, _p, _i, _l, _p, _i, _p, _p, _p, _l, _i, _p]),
-    'segf_bn_affine_table': (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
-    'segf_gemm_dw_db': (_i, [_i, _l, _l, _l, _p, _l, _p, _l, _p, _i, _l, _i, _p, _p, _p]),
-    'segf_gemm_dw_db_grouped': (_i, [_i, _i, _p, _p]),
-    'segf_layernorm_bwd_blocks': (_i, [_l, _i]),
-    'segf_colreduce_finalize_grouped': (_i, [_i, _p, _p]),
-    'segf_layernorm_fwd': (_i, [_i, _l, _i, _p, _p, _p, _f, _p, _p, _p, _p]),
-    'segf_layernorm_fwd_patch': (_i, [_i, _l, _i, _p, _p, _p, _f, _p, _p, _p, _p, _i, _i, _p]),
-    'segf_layernorm_bwd_patch': (_i, [_i, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _i, _i, _p]),
-    'segf_layernorm_bwd_ws': (_l, [_l, _i]),
-    'segf_layernorm_bwd': (_i, [_i, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
-    'segf_bn_ws': (_l, [_l, _i]),
-    'segf_bn_stats': (_i, [_i, _l, _i, _p, _p, _p, _p, _p, _f, _f, _p, _p]),
-    'segf_bn_apply': (_i, [_i, _l, _i, _p, _p, _p, _p, _p, _i, _p, _l, _p, _p]),
-    'segf_bn_bwd': (_i, [_i, _l, _i, _p, _p, _p, _p, _p, _p, _i, _p, _l, _i, _p, _p, _p, _p, _p]),
-    'segf_bn_cls_bwd_supported': (_i, [_i, _l, _i, _i, _l]),
-    'segf_bn_cls_bwd_ws': (_l, [_l, _i, _l]),
-    'segf_bn_cls_bwd': (_i, [_i, _l, _i, _i, _p, _l, _p, _l, _p, _p, _p, _p, _p, _i, _p, _l, _i, _p, _p, _p, _p, _p]),
-    'segf_bn_cls_bwd_dw_supported': (_i, [_i, _l, _i, _i, _l, _i]),
-    'segf_bn_cls_bwd_dw_ws': (_l, [_l, _i, _l]),
-    'segf_bn_cls_bwd_dw': (_i, [_i, _l, _i, _i, _p, _l, _p, _l, _p, _p, _p, _p, _p, _i, _p, _l, _i, _p, _p, _p, _p, _p, _l, _i, _p, _p]),
-    'segf_bn_cls_bwd_full_ws': (_l, [_l, _i, _i, _l]),
-    'segf_bn_cls_bwd_full': (_i, [_i, _l, _i, _i, _p, _l, _p, _l, _p, _p, _p, _p, _p, _i, _p, _l, _i, _p, _p, _p, _p, _p, _l, _i, _p, _p, _p]),
-    'segf_grn_ws': (_l, [_i, _l, _i, _i]),
-    'segf_grn_fwd': (_i, [_i, _i, _l, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
-    'segf_grn_bwd': (_i, [_i, _i, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
-    'segf_attention_fwd': (_i, [_i, _i, _i, _i, _i, _i, _p, _l, _p, _l, _p, _l, _f, _p, _l, _p, _p]),
-    'segf_attention_bwd_ws': (_l, [_i, _i, _i, _i, _i]),
-    'segf_attention_bwd': (_i, [_i, _i, _i, _i, _i, _i, _p, _l, _p, _l, _p, _l, _f, _p, _l, _p, _l, _p,
-                                _p, _l, _p, _l, _p, _l, _p, _p]),
-    'segf_dwconv3x3_gelu_fwd': (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
-    'segf_dwconv3x3_bwd_ws': (_l, [_i, _i, _i, _i]),
-    'segf_dwconv3x3_bwd_blocks': (_i, [_i, _i, _i, _i, _i]),
-    'segf_dwconv3x3_gelu_bwd': (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
-    'segf_dwconv7x7_fwd': (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
-    'segf_dwconv7x7_bwd_ws': (_l, [_i, _i, _i, _i]),
-    'segf_dwconv7x7_bwd': (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
-    'segf_conv3x3': (_i, [_i, _i, _i, _i, _i, _i, _p, _l, _p, _l, _p, _i, _l, _p, _i, _p, _p]),
-    'segf_gelu': (_i, [_i, _i, _p, _p, _p, _l, _p]),
-    'segf_rowdot': (_i, [_p, _l, _p, _l, _p, _p, _p, _l, _l, _p]),
-    'segf_adaptive_avgpool': (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
-    'segf_im2col': (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p]),
-    'segf_col2im': (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _l, _p, _p]),
-    'segf_bilinear_fwd': (_i, [_i, _i, _i, _i, _i, _p, _l, _i, _i, _p, _l, _i, _p]),
-    'segf_bilinear_bwd': (_i, [_i, _i, _i, _i, _i, _p, _l, _i, _i, _p, _l, _i, _p]),
-    'segf_bilinear_bwd_248': (_i, [_i, _i, _i, _i, _i, _p, _l, _p, _p, _p, _p]),
-    'segf_nearest_up': (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
-    'segf_upsample_add': (_i, [_i, _i, _i, _i, _i, _p, _l, _i, _p, _i, _i, _l, _p, _i, _i, _l, _p, _i, _i, _l, _p, _l, _i, _p]),
-    'segf_upsample_add_stats_ws': (_l, [_i, _i, _i, _i]),
-    'segf_upsample_add_stats': (_i, [_i, _i, _i, _i, _i, _p, _l, _i, _p, _i, _i, _l, _p, _i, _i, _l, _p, _i, _i, _l, _p, _l, _i, _p, _p, _p]),
-    'segf_fuse_map_248_supported': (_i, [_i, _i, _i, _i, _i, _i]),
-    'segf_fuse_map_248_ws': (_l, [_i, _i, _i, _i]),
-    'segf_fuse_map_248': (_i, [_i, _i, _i, _i, _i, _p, _l, _p, _l, _p, _l, _p, _l, _p, _l, _p, _l, _p, _p, _p]),
-    'segf_bn_stats_from_sums': (_i, [_p, _l, _i, _p, _p, _p, _p, _f, _f, _p]),
-    'segf_bilinear_to_nchw_f32': (_i, [_i, _i, _i, _i, _i, _p, _l, _i, _i, _p, _p]),
-    'segf_ce_dice_stats_floats': (_l, [_i, _i]),
-    'segf_ce_dice_lse_floats': (_l, [_i, _i, _i, _i, _i, _i, _i, _p, _l]),
-    'segf_ce_dice_fwd': (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _l, _p, _l, _p, _i, _p, _p, _p, _p]),
-    'segf_ce_dice_bwd_ws': (_l, [_i, _i, _i, _i, _i, _i, _i]),
-    'segf_ce_dice_bwd': (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _l, _p, _l, _p, _i, _p, _p, _p, _l, _p, _p, _p]),
-    'segf_debug_wave_reduce16': (_i, [_p, _p, _p]),
-    'segf_argmax_confmat': (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _l, _p, _l, _p, _p, _p, _p, _p]),
-    'segf_confmat_pairs': (_i, [_p, _p, _l, _i, _l, _p, _p, _p, _p]),
-    'segf_agc_adamw': (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _f, _f, _f, _f, _f, _i, _f, _f, _p]),
-    'segf_clip_grad_ws': (_l, []),
-    'segf_clip_grad': (_i, [_p, _l, _i, _f, _p, _p]),
-    'segf_zero': (_i, [_p, _l, _p]),
-    'segf_add_i64': (_i, [_p, _l, _p]),
-    'segf_hist_accum': (_i, [_p, _p, _l, _i, _p]),
-    'segf_debug_spin': (_i, [_l, _p]),
-    'segf_gemm8_option': (_i, [_i, _i]),
-    'segf_bernoulli_scale': (_i, [_p, _p, _l, _l, _p, _p]),
-    'segf_layernorm_bwd_fused': (_i, [_i, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
-    'segf_layernorm_bwd_scaled': (_i, [_i, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p]),
-    'segf_quant_rows_fp8': (_i, [_i, _l, _i, _p, _l, _p, _l, _p, _p]),
-    'segf_gemm_fp8_supported': (_i, [_l, _l, _l]),
-    'segf_quant_tensor_fp8': (_i, [_i, _i, _l, _i, _p, _l, _p, _l, _p, _p, _p]),
-    'segf_conv3x3_fp8_supported': (_i, [_i, _i, _i, _i, _i, _i]),
-    'segf_conv3x3_fp8': (_i, [_i, _i, _i, _i, _i, _i, _p, _l, _p, _p, _l, _p, _p, _l, _p]),
-    'segf_conv3x3_fp8_wgrad_supported': (_i, [_i, _i, _i, _i, _i]),
-    'segf_conv3x3_fp8_wgrad': (_i, [_i, _i, _i, _i, _i, _p, _l, _p, _p, _l, _p, _p, _l, _i, _p, _p]),
-    'segf_gemm_fp8': (_i, [_l, _l, _l, _p, _l, _p, _p, _l, _p, _p, _p, _l, _p, _l, _p, _l, _p]),
-    'segf_linear_fp8_supported': (_i, [_i, _l, _l, _l]),
-    'segf_linear_fp8': (_i, [_i, _l, _l, _l, _p, _l, _p, _p, _l, _p, _p, _l, _p, _p, _l, _p, _l, _p]),
-    'segf_linear_fp8_wgrad_splitk': (_i, [_l, _l, _l]),
-    'segf_linear_fp8_wgrad': (_i, [_l, _l, _l, _p, _l, _p, _p, _l, _p, _p, _l, _i, _p, _p]),
-    'segf_input_train': (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
-    'segf_input_val_ws': (_l, [_i, _i, _i, _i]),
-    'segf_input_val': (_i, [_p, _l, _p, _l, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
-    'segf_infer_preprocess': (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p]),
-    'segf_event_create': (_i, [C.POINTER(C.c_void_p)]),
-    'segf_event_destroy': (_i, [_p]),
-    'segf_event_record': (_i, [_p, _p, _i]),
-    'segf_stream_wait_event': (_i, [_p, _p]),
-    'segf_version': (C.c_char_p, []),
-    'segf_policy_count': (_i, []),
-    'segf_policy_describe': (_i, [_i, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_char_p)]),
-    'segf_policy_get': (_i, [C.c_char_p]),
-    'segf_policy_set': (_i, [C.c_char_p, _i]),
-    'segf_policy_reload': (None, []),
-    'segf_trace_begin': (None, [_i]),
-    'segf_trace_end': (_i, [C.c_char_p, _i]),
-}
+_SCALAR = {'int': _i, 'int32_t': _i, 'int64_t': _l, 'float': _f}
+_POINTEE = {'void', 'char', 'int', 'int32_t', 'int64_t', 'uint8_t', 'uint64_t', 'float'}
+
+
+def _ctype(ctype, where, structs):
+    """ctypes type of one C type of the header ('const' ignored).  Strict: a type outside the rule raises, nothing becomes c_void_p
+    by default."""
+    t = re.sub(r'\bconst\b', ' ', ctype).replace('*', ' * ').split()
+    if t and all(w == '*' for w in t[1:]):
+        base, stars = t[0], len(t) - 1
+        if stars == 0 and base in _SCALAR:
+            return _SCALAR[base]
+        if stars == 1 and base == 'char':
+            return C.c_char_p
+        if stars == 1 and (base in _POINTEE or base in structs):
+            return _p
+        if stars > 1:
+            return C.POINTER(_ctype(base + '*' * (stars - 1), where, structs))
+    raise RuntimeError(f'include/segfac.h: {where}: the C type {" ".join(ctype.split())!r} has no ctypes mapping in hip.py')
+
+
+def _declarators(decl, where, structs):
+    """[(name, ctypes type)] of one declaration 'T a, *b, c[3]'."""
+    m = re.fullmatch(r'\s*((?:const\s+)?\w+)(.*)', decl, re.S)
+    ds = [re.fullmatch(r'\s*(\**)\s*(\w+)\s*(?:\[(\d+)\])?\s*', d) for d in m.group(2).split(',')] if m else [None]
+    if not all(ds):
+        raise RuntimeError(f'include/segfac.h: {where}: cannot read {" ".join(decl.split())!r}')
+    out = []
+    for d in ds:
+        stars, name, n = d.groups()
+        t = _ctype(m.group(1) + stars, f'{where} {name}', structs)
+        out.append((name, t * int(n) if n else t))
+    return out
+
+
+def _parse_header(text):
+    """({entry point: (restype, [argtypes])}, {typedef name: ctypes.Structure}) of every declaration, as a C compiler reads the header.
+    Anything at file scope other than a `typedef struct` or a segf_* function declaration raises."""
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    text = re.sub(r'#ifdef __cplusplus.*?#endif', ' ', text, flags=re.S)       # the extern "C" wrapper
+    text = re.sub(r'^\s*#.*$', ' ', text, flags=re.M)
+    structs, decls = {}, {}
+
+    def struct(m):
+        fields = [f for d in m.group(1).split(';') if d.strip() for f in _declarators(d, m.group(2), structs)]
+        structs[m.group(2)] = type(m.group(2), (C.Structure,), {'_fields_': fields, '__doc__': f'{m.group(2)} of include/segfac.h'})
+        return ';'
+    text = re.sub(r'typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;', struct, text, flags=re.S)
+    for stmt in filter(str.strip, text.split(';')):
+        m = re.fullmatch(r'\s*(.*?)\b(segf_\w+)\s*\((.*)\)\s*', stmt, re.S)
+        if not m:
+            raise RuntimeError(f'include/segfac.h: cannot read the declaration {" ".join(stmt.split())!r}')
+        ret, name, args = m.groups()
+        res = None if ret.split() == ['void'] else _ctype(ret, name, structs)
+        decls[name] = (res, [] if args.split() == ['void'] else
+                       [t for a in args.split(',') for _, t in _declarators(a, name, structs)])
+    return decls, structs
+
+
+def _read_header():
+    if not os.path.isfile(HEADER_PATH):
+        raise RuntimeError(f'{HEADER_PATH} is missing: the ctypes binding of libsegfac_hip.so is derived from it; use the package '
+                           f'from the repository tree (include/ next to segmentation_factory_amd/).')
+    with open(HEADER_PATH) as fh:
+        return _parse_header(fh.read())
+
+
+_DECLS, _STRUCTS = _read_header()
+SegfPrepItem = _STRUCTS['SegfPrepItem']                 # one job of segf_prep_grouped
+SegfDwItem = _STRUCTS['SegfDwItem']                     # one layer of segf_gemm_dw_db_grouped
+SegfFinalizeItem = _STRUCTS['SegfFinalizeItem']         # one member of segf_colreduce_finalize_grouped
+InputSample = _STRUCTS['segf_input_sample']             # one image of segf_input_train (72 bytes)
 
 
 def lib():
@@ -148,7 +104,7 @@ def lib():
                 f'{LIB_PATH} is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                 f'or `make -C segmentation_factory_amd/csrc`. There is no CPU/eager fallback.')
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _PROTOS.items():
+        for name, (res, args) in _DECLS.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -157,7 +113,7 @@ def lib():
 
 
 def exported_symbols():
-    return sorted(_PROTOS)
+    return sorted(_DECLS)
 
 
 # ---- dispatch policy (csrc/policy.h; documented in include/segfac.h) and launch trace -------------------------------------------
@@ -309,13 +265,6 @@ def permute021(x: torch.Tensor, A: int, Bd: int, Cd: int, out_dtype: torch.dtype
     return out
 
 
-class SegfPrepItem(C.Structure):
-    """include/segfac.h: one job of segf_prep_grouped"""
-    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('rows', C.c_int64), ('cols', C.c_int64), ('ld_src', C.c_int64),
-                ('ld_dst', C.c_int64), ('pb', C.c_int64), ('pc', C.c_int64), ('op', C.c_int32), ('src_dt', C.c_int32),
-                ('dst_dt', C.c_int32), ('reserved', C.c_int32)]
-
-
 def _as2d(src, dst):
     if src is not None and src.ndim == 1:
         src = src.view(1, -1) if src.stride(0) == 1 else src.unsqueeze(1)
@@ -431,13 +380,6 @@ def gemm_dw_db(dy: torch.Tensor, x: torch.Tensor, M: int, N: int, K: int, split_
         dt_of(dy), M, N, K, _ptr(dy), dy.stride(0), _ptr(x), x.stride(0), _ptr(dw), dt_of(dw), dw.stride(0), split_k, _ptr(ws),
         _ptr(db), _stream())), 'segf_gemm_dw_db')
     return dw, db
-
-
-class SegfDwItem(C.Structure):
-    """include/segfac.h: one layer of segf_gemm_dw_db_grouped"""
-    _fields_ = [('M', C.c_int64), ('N', C.c_int64), ('K', C.c_int64), ('dy', C.c_void_p), ('lddy', C.c_int64), ('x', C.c_void_p),
-                ('ldx', C.c_int64), ('dw', C.c_void_p), ('lddw', C.c_int64), ('db', C.c_void_p), ('ws', C.c_void_p), ('split_k', C.c_int),
-                ('shared_split', C.c_int)]
 
 
 def gemm_dw_db_grouped(items, shared_split=False):
@@ -774,11 +716,6 @@ def bernoulli_scale(state, keep_prob, n, row_len):
     out = torch.empty(n, dtype=torch.float32, device=state.device)
     _chk(lib().segf_bernoulli_scale(_ptr(state), _ptr(keep_prob), n, row_len, _ptr(out), _stream()), 'segf_bernoulli_scale')
     return out
-
-
-class SegfFinalizeItem(C.Structure):
-    """include/segfac.h: one member of segf_colreduce_finalize_grouped"""
-    _fields_ = [('partial', C.c_void_p), ('out', C.c_void_p), ('len', C.c_int64), ('nblk', C.c_int), ('scatter_c', C.c_int)]
 
 
 def colreduce_finalize_grouped(items):
@@ -1118,13 +1055,6 @@ def nearest_up(x, B, h, w, Cc, H, W, base=None, bwd=False):
     out = torch.empty(((B * h * w) if bwd else (B * H * W), Cc), dtype=x.dtype, device=x.device)
     _chk(lib().segf_nearest_up(dt_of(x), int(bwd), B, h, w, Cc, H, W, _ptr(x), _ptr(base), _ptr(out), _stream()), 'segf_nearest_up')
     return out
-
-
-class InputSample(C.Structure):
-    """segf_input_sample of include/segfac.h (72 bytes)."""
-    _fields_ = [('img', C.c_uint64), ('lbl', C.c_uint64), ('img_stride', C.c_int64), ('lbl_stride', C.c_int64),
-                ('src_h', C.c_int32), ('src_w', C.c_int32), ('top', C.c_int32), ('left', C.c_int32),
-                ('flip', C.c_int32), ('order', C.c_int32), ('factor', C.c_float * 3), ('reserved', C.c_int32)]
 
 
 def input_train(samples, B, H, W, mean3, std3, label_lut, out_img=None, out_lbl=None):

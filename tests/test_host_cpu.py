@@ -26,6 +26,60 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f'{name} declared in include/segfac.h but not exported'
     assert set(hip.exported_symbols()) == set(declared)
     assert b'gfx950' in lib.segf_version()
+    # the binding is parsed from the header: no declaration may be skipped by the parser
+    code = re.sub(r'/\*.*?\*/', ' ', header, flags=re.S)
+    assert len(hip._DECLS) == len(re.findall(r'\bsegf_\w+\s*\(', code))
+
+
+def test_header_structs_match_the_c_compiler(tmp_path):
+    """sizeof / offsetof / field sizes of the parsed ctypes structs against a C compiler reading include/segfac.h."""
+    import ctypes as C
+    from segmentation_factory_amd import hip
+    assert set(hip._STRUCTS) == {'SegfPrepItem', 'SegfDwItem', 'SegfFinalizeItem', 'segf_input_sample'}
+    assert hip.InputSample is hip._STRUCTS['segf_input_sample'] and C.sizeof(hip.InputSample) == 72
+    lines, expect = [], []
+    for name, st in sorted(hip._STRUCTS.items()):
+        lines.append(f'printf("{name} %zu\\n", sizeof({name}));')
+        expect.append(f'{name} {C.sizeof(st)}')
+        for field, _ in st._fields_:
+            lines.append(f'printf("{name}.{field} %zu %zu\\n", offsetof({name}, {field}), sizeof((({name}*)0)->{field}));')
+            expect.append(f'{name}.{field} {getattr(st, field).offset} {getattr(st, field).size}')
+    src = tmp_path / 'layout.c'
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "segfac.h"\nint main(void) {\n' + '\n'.join(lines)
+                   + '\nreturn 0;\n}\n')
+    cc = '/opt/rocm/llvm/bin/clang' if os.path.isfile('/opt/rocm/llvm/bin/clang') else 'cc'
+    subprocess.run([cc, '-std=c11', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(tmp_path / 'layout')], check=True)
+    out = subprocess.run([str(tmp_path / 'layout')], check=True, capture_output=True, text=True).stdout
+    assert out.split('\n')[:-1] == expect
+
+
+def test_header_parser_type_rule():
+    import ctypes as C
+    from segmentation_factory_amd import hip
+    decls, structs = hip._parse_header('''
+        #include <stdint.h>
+        /* int segf_commented_out(size_t n); */
+        typedef struct T { const uint8_t* p; int64_t a, b; int32_t c; float f[3]; } T;
+        const char* segf_a(int a, int32_t b, int64_t c, float d, char* e, void* f, const float* g, int* h, int64_t* i, uint64_t* j,
+                           const T* t);
+        void segf_b(void);
+        int64_t segf_c(void** a, const char** b);
+        #ifdef __cplusplus
+        }
+        #endif''')
+    assert decls == {'segf_a': (C.c_char_p, [C.c_int, C.c_int, C.c_int64, C.c_float, C.c_char_p] + [C.c_void_p] * 6),
+                     'segf_b': (None, []),
+                     'segf_c': (C.c_int64, [C.POINTER(C.c_void_p), C.POINTER(C.c_char_p)])}
+    assert structs['T']._fields_ == [('p', C.c_void_p), ('a', C.c_int64), ('b', C.c_int64), ('c', C.c_int), ('f', C.c_float * 3)]
+    assert decls['segf_a'][1][0] is hip._i and decls['segf_c'][0] is hip._l        # dispatch.py compares by identity
+
+
+@pytest.mark.parametrize('decl', ['int segf_x(size_t n);', 'int segf_x(size_t* n);', 'unsigned segf_x(int n);', 'int segf_x(int);',
+                                  'int segf_x(unsigned int n);', 'int other_x(int n);', 'typedef struct { long n; } segf_x;'])
+def test_header_parser_rejects_what_it_cannot_map(decl):
+    from segmentation_factory_amd import hip
+    with pytest.raises(RuntimeError, match='segf_x|other_x'):
+        hip._parse_header(decl)
 
 
 @pytest.mark.parametrize('nc', [19, 150])
