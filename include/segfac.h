@@ -57,6 +57,10 @@ int segf_prep_grouped(int n, const SegfPrepItem* items, void* stream);
 /* y[r][c] = x[r][c] * scale[r / rows_per_group]   (DropPath backward, models/layers/drop_path.py:18-25) */
 int segf_scale_rows(int dt, const void* x, int64_t ldx, void* y, int64_t ldy, const float* scale,
                     int64_t rows, int64_t cols, int64_t rows_per_group, void* stream);
+/* y[r][c] = x[r][c] * scale[r * cols + c], scale fp32 and dense: nn.Dropout per element (heads/deeplabv3.py:56,115) with the
+ * keep-scales of segf_bernoulli_scale; the backward is the same call on the gradient.  cols % 8 == 0. */
+int segf_mul_scale(int dt, const void* x, int64_t ldx, const float* scale, void* y, int64_t ldy, int64_t rows, int64_t cols,
+                   void* stream);
 /* y = a + b  (residual / gradient fan-in), 2-D with leading dims */
 int segf_add(int dt, const void* a, int64_t lda, const void* b, int64_t ldb, void* y, int64_t ldy,
              int64_t rows, int64_t cols, void* stream);
@@ -343,6 +347,24 @@ int segf_conv3x3_pick_splitk(int Cin, int Cout, int64_t P);
 int segf_conv3x3(int mode, int B, int H, int W, int Cin, int Cout, const void* x, int64_t ldx, const void* w, int64_t ldw,
                  void* y, int y_dt, int64_t ldy, const float* bias, int split_k, float* ws, void* stream);
 
+/* ---- 3x3 conv with DILATION, stride 1, padding = dilation, no bias, NHWC, as an implicit MFMA GEMM without an im2col buffer
+ * (csrc/conv_dilated.hip): _ASPPConv of DeepLabV3's ASPP, heads/deeplabv3.py:65-75 (rates 12 / 24 / 36, :51,105-108).  dt = SEGF_BF16
+ * (v_mfma_f32_16x16x32_bf16) or SEGF_F32 (the f32-input matrix instruction: an exact fp32 fma chain); Cin, Cout multiples of 8;
+ * P = B*H*W pixels; x and y may be column slices of wider buffers (ldx, ldy).  off(tap) = ((ty - 1) * dilation, (tx - 1) * dilation).
+ *   mode 0: y[P][ldy] (dt)  = sum_{tap, ci} x[p + off(tap)][ci] * w[co][tap * Cin + ci]                     w [Cout][9*Cin] (ldw)
+ *   mode 1: y = dx[P][ldy] (dt): x := dy[P][ldx], w := wt[Cin][9*Cout] ([ci][tap][co]), the tap offsets negated
+ *   mode 2: y = dw fp32 [Cout][9*Cin] (ldy): x[P][ldx], w := dy[P][ldw]; the pixels are split into split_k slices
+ *           (segf_conv3x3_dil_pick_splitk) with ws >= split_k * Cout * 9 * Cin floats when split_k > 1, summed by a reduce pass
+ * Only the taps that can touch the map are walked (|ty - 1| * dilation < H and |tx - 1| * dilation < W: segf_conv3x3_dil_live_taps; at
+ * 16 x 16 the rates 24 and 36 are the centre tap alone), and a workgroup skips a live tap none of its pixels reaches.  The weight
+ * gradient of a dead tap is written as zeros.  SEGFAC_DILCONV_NO_CULL walks all nine taps.  Shapes whose element offsets do not fit
+ * 32 bits return SEGF_ERR_SHAPE. */
+int segf_conv3x3_dil_live_taps(int H, int W, int dilation, int* taps /*[9]: ty * 3 + tx*/);
+int segf_conv3x3_dil_supported(int dt, int mode, int B, int H, int W, int Cin, int Cout, int dilation);
+int segf_conv3x3_dil_pick_splitk(int B, int H, int W, int Cin, int Cout, int dilation);
+int segf_conv3x3_dil(int dt, int mode, int B, int H, int W, int Cin, int Cout, int dilation, const void* x, int64_t ldx,
+                     const void* w, int64_t ldw, void* y, int64_t ldy, int split_k, float* ws, void* stream);
+
 /* y = gelu_erf(u) (mode 0) or dy * gelu_erf'(u) (mode 1), flat, n % 8 == 0 (nn.GELU, convnext.py:32,43) */
 int segf_gelu(int dt, int mode, const void* u, const void* dy, void* y, int64_t n, void* stream);
 /* out[r] = sum_c a[r][c] b[r][c] (+ extra_a[r] extra_b[r]), fp32: d gamma of a layer scale folded into the weights */
@@ -549,6 +571,7 @@ int segf_input_val(const uint8_t* img, int64_t img_stride, const uint8_t* lbl, i
  *   SEGFAC_NO_FP8_CONV           segf_conv3x3_fp8*_supported answer 0
  *   SEGFAC_NO_FP8_WGRAD          fp8 3 x 3 convolutions keep a bf16 weight gradient
  *   SEGFAC_NO_FP8_LINEAR         segf_linear_fp8_supported answers 0
+ *   SEGFAC_DILCONV_NO_CULL       dilated 3 x 3 convolution (segf_conv3x3_dil): all nine taps are walked, with zero loads where a tap leaves the image
  *   SEGFAC_ATTN_NO_MFMA          attention on the VALU reference kernels (attention.hip) also in bf16
  *   SEGFAC_ATTN_F32_NO_MFMA      fp32 attention forward on the vector kernel (one query per lane) instead of the f32 matrix instruction
  *   SEGFAC_ATTN64_PRESCALE       head dim 64, >= 128 keys: scale log2(e) rides on the Q fragments (bf16(q c), one more rounding per q element) and -max / -lse are the score accumulators' initial values, instead of one multiply-add per score: forward + query-side backward, +8 % / +2 % per kernel, attention error x 1.2 - 2.3

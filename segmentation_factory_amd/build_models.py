@@ -59,10 +59,17 @@ class SegmentationModel(BaseSegModel):
                 raise KeyError(f'backbone {backbone!r} is not available in the MI355X path; have {sorted(backbone_registry)}')
             self.backbone = backbone_registry[backbone]()
             name_for_width = backbone
-        if seg_head not in head_dict:
-            raise KeyError(f'seg_head {seg_head!r} is not available in the MI355X path; have {sorted(head_dict)}')
-        width = 128 if ('tiny' in name_for_width or 'small' in name_for_width) else 768
-        self.decode_head = head_dict[seg_head](self.backbone.channels, width, num_classes)
+        if 'deeplabv3' in seg_head.lower():                     # the reference's rule (build_models.py:47-51); no width rule here
+            if aux_for_deeplab:
+                raise NotImplementedError('aux_for_deeplab=True is not available: the reference model returns a dict on that path, which '
+                                          'its own forward (build_models.py:65) cannot resize; build the model without the auxiliary head')
+            ch = self.backbone.channels
+            self.decode_head = _heads.DeepLabV3(ch[-1], ch[-2], num_classes, False)
+        else:
+            if seg_head not in head_dict:
+                raise KeyError(f'seg_head {seg_head!r} is not available in the MI355X path; have {sorted(head_dict) + ["deeplabv3"]}')
+            width = 128 if ('tiny' in name_for_width or 'small' in name_for_width) else 768
+            self.decode_head = head_dict[seg_head](self.backbone.channels, width, num_classes)
         self.set_compute_dtype(compute_dtype)
         if pretrained_backbone:
             if os.path.exists(pretrained_backbone):

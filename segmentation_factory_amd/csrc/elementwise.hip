@@ -230,6 +230,38 @@ extern "C" int segf_add(int dt, const void* a, int64_t lda, const void* b, int64
     return 0;
 }
 
+// ---- per-element scale: nn.Dropout (heads/deeplabv3.py:56,115) forward and backward -------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(256) mul_scale_kernel(const T* __restrict__ x, int64_t ldx, const float* __restrict__ scale, T* __restrict__ y,
+                                                        int64_t ldy, int64_t rows, int64_t cols) {
+    const int64_t nchunk = cols / 8, total = rows * nchunk;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int64_t r = i / nchunk;
+        const int64_t c0 = (i - r * nchunk) * 8;
+        float v[8], s[8];
+        load8<T>(x + r * ldx + c0, v);
+        load8f(scale + r * cols + c0, s);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] *= s[j];
+        store8<T>(y + r * ldy + c0, v);
+    }
+}
+
+extern "C" int segf_mul_scale(int dt, const void* x, int64_t ldx, const float* scale, void* y, int64_t ldy, int64_t rows, int64_t cols,
+                              void* stream) {
+    if (rows <= 0 || cols <= 0) return 0;
+    if (cols % 8 || ldx < cols || ldy < cols || !x || !y || !scale) return SEGF_ERR_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = (int)imin64(cdiv64(rows * (cols / 8), 256), 4096);
+    SEGF_DISPATCH_DT(dt, T, {
+        if (!vec_ok_host<T>(x, ldx) || !vec_ok_host<T>(y, ldy) || (uintptr_t)scale % 16) return SEGF_ERR_SHAPE;
+        hipLaunchKernelGGL((mul_scale_kernel<T>), dim3(blocks), dim3(256), 0, st, (const T*)x, ldx, scale, (T*)y, ldy, rows, cols);
+    })
+    SEGF_CHECK_LAUNCH();
+    return 0;
+}
+
 // ---- column sum ----------------------------------------------------------------------------------------
 template <typename T> struct ColsumF {
     const T* x; int64_t ld; bool vec;

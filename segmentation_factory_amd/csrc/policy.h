@@ -50,6 +50,8 @@
     X(no_fp8_conv, "SEGFAC_NO_FP8_CONV", 0, "segf_conv3x3_fp8*_supported answer 0")                                                      \
     X(no_fp8_wgrad, "SEGFAC_NO_FP8_WGRAD", 0, "fp8 3 x 3 convolutions keep a bf16 weight gradient")                                      \
     X(no_fp8_linear, "SEGFAC_NO_FP8_LINEAR", 0, "segf_linear_fp8_supported answers 0")                                                   \
+    /* ---- dilated 3 x 3 convolution (conv_dilated.hip) ---- */                                                                         \
+    X(dilconv_no_cull, "SEGFAC_DILCONV_NO_CULL", 0, "dilated 3 x 3 convolution: all nine taps are walked, with zero loads where a tap leaves the image, instead of the live taps only") \
     /* ---- attention (attention.hip, attention_mfma.hip) ---- */                                                                        \
     X(attn_no_mfma, "SEGFAC_ATTN_NO_MFMA", 0, "attention on the VALU reference kernels (attention.hip) also in bf16")                    \
     X(attn_f32_no_mfma, "SEGFAC_ATTN_F32_NO_MFMA", 0, "fp32 attention forward on the vector kernel (one query per lane) instead of the f32 matrix instruction") \

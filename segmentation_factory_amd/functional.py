@@ -1315,6 +1315,82 @@ def conv3x3(x, weight, B, H, W, fp8=False):
     return ConvPatchFn.apply(x, weight, None, (B, H, W, weight.shape[1], 3, 1, 1), False, x.dtype)
 
 
+@direct_grads(1)
+class DilatedConv3x3Fn(Function):
+    """3x3 / stride 1 / padding = dilation convolution without bias on NHWC tokens as an implicit MFMA GEMM over the taps that can touch
+    the map (_ASPPConv, heads/deeplabv3.py:65-75), bf16 or fp32.  x may be a column slice of a wider buffer."""
+
+    @staticmethod
+    def forward(ctx, x, weight, B, H, W, dilation):
+        x = _rowmajor(x)
+        O, I = weight.shape[0], weight.shape[1]
+        wsrc = weight.detach().contiguous()
+        cdt = x.dtype
+
+        def make_wm():
+            t = torch.empty((O, 9, I), dtype=cdt, device=x.device)
+            return t, [('perm', wsrc, t, O, I, 9, I)]
+        wm = derived_weight(wsrc, ('conv3x3', cdt), make_wm).view(O, 9 * I)                         # [O][(ky,kx)][ci]
+        y = hip.conv3x3_dil(0, x, wm, B, H, W, I, O, dilation)
+        ctx.save_for_backward(x, weight.detach())
+        ctx.meta = (B, H, W, I, O, weight.shape, dilation)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        B, H, W, I, O, wshape, dilation = ctx.meta
+        dy = _rowmajor(dy)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            wt = hip.permute021(w.reshape(1, O, I * 9), 1, O, I * 9, dy.dtype).view(I, 9 * O)             # [ci][(ky,kx)][co]
+            dx = hip.conv3x3_dil(1, dy, wt, B, H, W, I, O, dilation)
+        if ctx.needs_input_grad[1]:
+            dwm = hip.conv3x3_dil(2, x, dy, B, H, W, I, O, dilation)                                        # [O][(ky,kx)][ci] fp32
+            dw = hip.permute021(dwm.view(O, 9, I), O, 9, I, torch.float32).view(wshape)
+        return dx, dw, None, None, None, None
+
+
+def conv3x3_dilated(x, weight, B, H, W, dilation):
+    """Conv2d(c1, c2, 3, padding=dilation, dilation=dilation, bias=False).  dilation 1 is the plain 3x3 convolution (conv3x3)."""
+    dilation = int(dilation)
+    if dilation == 1:
+        return conv3x3(x, weight, B, H, W)
+    O, I = weight.shape[0], weight.shape[1]
+    if not hip.conv3x3_dil_supported(x.dtype, 0, B, H, W, I, O, dilation):
+        raise ValueError(f'conv3x3_dilated: no kernel for {x.dtype} B={B} H={H} W={W} {I}->{O} dilation={dilation} '
+                         '(channels must be multiples of 8, dilation >= 1)')
+    return DilatedConv3x3Fn.apply(x, weight, B, H, W, dilation)
+
+
+class DropoutFn(Function):
+    """nn.Dropout per element (heads/deeplabv3.py:56,115): y = x * scale with scale = keep / p_keep; the backward multiplies by the
+    same scales."""
+
+    @staticmethod
+    def forward(ctx, x, scale):
+        ctx.save_for_backward(scale)
+        return hip.mul_scale(_rowmajor(x), scale)
+
+    @staticmethod
+    def backward(ctx, dy):
+        scale, = ctx.saved_tensors
+        return hip.mul_scale(_rowmajor(dy), scale), None
+
+
+def dropout(x, p, training, owner, override=None):
+    """Elementwise dropout with rate p on token rows.  Eval mode and p == 0 apply nothing.  override: a 0 / 1 keep mask of x's shape
+    (tests); otherwise the keep-scales come from the device-side generator (stochastic_scales), fresh on every graph replay."""
+    if not training or p <= 0.0:
+        return x
+    keep = 1.0 - float(p)
+    if override is not None:
+        scale = (override.to(device=x.device, dtype=torch.float32) / keep).reshape(x.shape).contiguous()
+    else:
+        scale = stochastic_scales(owner, (keep,), x.shape[0] * x.shape[1], x.device).view(x.shape)
+    return DropoutFn.apply(x, scale)
+
+
 class GeluFn(Function):
     """nn.GELU (erf) between ConvNeXt's pointwise linears (convnext.py:32,43)."""
 

@@ -8,7 +8,7 @@ from . import functional as Fh
 from .backbones import TokenMap, tokens_from_nchw
 from .containers import BatchNormWeights, ConvWeights, LinearWeights
 
-__all__ = ['SegFormerHead', 'UPerHead', 'FPNHead']
+__all__ = ['SegFormerHead', 'UPerHead', 'FPNHead', 'DeepLabV3']
 
 DROPOUT2D_P = 0.1
 
@@ -239,6 +239,100 @@ class FPNHead(nn.Module):
             else:
                 out = _bn_relu(y, bn, self.training)
         logits = Fh.linear(out, self.conv_seg.weight, self.conv_seg.bias, pad_to=(nc + 7) // 8 * 8)
+        return TokenMap(logits, B, H, W)
+
+    def forward(self, features):
+        tms = [f if isinstance(f, TokenMap) else tokens_from_nchw(f, self.compute_dtype) for f in features]
+        return self.forward_tokens(tms).nchw()
+
+
+ASPP_RATES = (12, 24, 36)
+ASPP_WIDTH = 256
+
+
+class _ASPPConv(nn.Module):
+    """3x3 conv with padding = dilation = rate (no bias) + BatchNorm2d + ReLU (heads/deeplabv3.py:65-75)."""
+
+    def __init__(self, c1, c2, rate):
+        super().__init__()
+        self.block = nn.Sequential(ConvWeights(c1, c2, 3, padding=rate, dilation=rate, bias=False), BatchNormWeights(c2), nn.ReLU(True))
+        self.rate = rate
+
+
+class _AsppPooling(nn.Module):
+    """Global average -> 1x1 conv -> BatchNorm2d -> ReLU, broadcast back to the map (heads/deeplabv3.py:78-92)."""
+
+    def __init__(self, c1, c2):
+        super().__init__()
+        self.gap = nn.Sequential(nn.AdaptiveAvgPool2d(1), ConvWeights(c1, c2, 1, bias=False), BatchNormWeights(c2), nn.ReLU(True))
+
+
+class _ASPP(nn.Module):
+    """Atrous spatial pyramid pooling (heads/deeplabv3.py:95-126): 1x1 branch, three dilated 3x3 branches, the pooled branch, concat,
+    1x1 projection + BatchNorm2d + ReLU + Dropout(0.5)."""
+
+    def __init__(self, c1, rates=ASPP_RATES, c2=ASPP_WIDTH):
+        super().__init__()
+        self.b0 = nn.Sequential(ConvWeights(c1, c2, 1, bias=False), BatchNormWeights(c2), nn.ReLU(True))
+        self.b1 = _ASPPConv(c1, c2, rates[0])
+        self.b2 = _ASPPConv(c1, c2, rates[1])
+        self.b3 = _ASPPConv(c1, c2, rates[2])
+        self.b4 = _AsppPooling(c1, c2)
+        self.project = nn.Sequential(ConvWeights(5 * c2, c2, 1, bias=False), BatchNormWeights(c2), nn.ReLU(True), nn.Dropout(0.5))
+
+    def tokens(self, x: TokenMap, training, override):
+        B, H, W = x.B, x.H, x.W
+        xs = Fh.fork(x.data, 5)                                             # all five branches read the top feature map
+        outs = [_bn_relu(Fh.linear(xs[0], self.b0[0].weight), self.b0[1], training)]
+        for k, br in enumerate((self.b1, self.b2, self.b3)):
+            conv, bn = br.block[0], br.block[1]
+            outs.append(_bn_relu(Fh.conv3x3_dilated(xs[1 + k], conv.weight, B, H, W, br.rate), bn, training))
+        pooled = Fh.adaptive_avgpool(xs[4], B, H, W, 1)                     # [B, C1]
+        outs.append(_bn_relu(Fh.linear(pooled, self.b4.gap[1].weight), self.b4.gap[2], training))
+        # align_corners=True from a 1 x 1 source (deeplabv3.py:91): every pixel takes the sample's one value
+        cat = Fh.resize_concat(outs, [(H, W)] * 4 + [(1, 1)], [False] * 4 + [True], (B, H, W))
+        y = _bn_relu(Fh.linear(cat, self.project[0].weight), self.project[1], training)
+        drop = self.project[3]
+        return Fh.dropout(y, drop.p, training, drop, None if override is None else override.get('dropout_aspp'))
+
+
+class _DeepLabHead(nn.Module):
+    """ASPP, then 3x3 conv + BatchNorm2d + ReLU + Dropout(0.1) + 1x1 classifier (heads/deeplabv3.py:48-62)."""
+
+    def __init__(self, c1, num_classes):
+        super().__init__()
+        self.aspp = _ASPP(c1)
+        self.block = nn.Sequential(ConvWeights(ASPP_WIDTH, ASPP_WIDTH, 3, padding=1, bias=False), BatchNormWeights(ASPP_WIDTH), nn.ReLU(True),
+                                   nn.Dropout(0.1), ConvWeights(ASPP_WIDTH, num_classes, 1))
+
+
+class DeepLabV3(nn.Module):
+    """DeepLabV3 decode head (models/heads/deeplabv3.py:7-44; built by models/build_models.py:47-51 as
+    ``DeepLabV3(channels[-1], channels[-2], num_classes, aux)``): ASPP on the last feature map, logits at its stride (32).
+    The auxiliary FCN head is not built: in the reference that path returns a dict which build_models.py:65 hands to F.interpolate."""
+
+    def __init__(self, in_channels: int, aux_channels: int, num_classes: int = 19, aux: bool = False):
+        super().__init__()
+        if aux:
+            raise NotImplementedError('DeepLabV3(aux=True): the auxiliary FCN head is not available (the reference model returns a dict '
+                                      'on that path, which its own forward cannot resize)')
+        self.head = _DeepLabHead(in_channels, num_classes)
+        self.aux = False
+        self.embed_dim, self.num_classes = ASPP_WIDTH, num_classes
+        self.compute_dtype = torch.bfloat16
+        self.stochastic_override = None       # tests: {'dropout_aspp': keep[B*H*W, 256], 'dropout_cls': keep[B*H*W, 256]}
+
+    def forward_tokens(self, feats):
+        tr = self.training
+        top = feats[-1]
+        B, H, W = top.B, top.H, top.W
+        nc = self.num_classes
+        ov = self.stochastic_override
+        x = self.head.aspp.tokens(top, tr, ov)
+        blk = self.head.block
+        x = _bn_relu(Fh.conv3x3(x, blk[0].weight, B, H, W), blk[1], tr)
+        x = Fh.dropout(x, blk[3].p, tr, blk[3], None if ov is None else ov.get('dropout_cls'))
+        logits = Fh.linear(x, blk[4].weight, blk[4].bias, pad_to=(nc + 7) // 8 * 8)
         return TokenMap(logits, B, H, W)
 
     def forward(self, features):

@@ -981,6 +981,52 @@ def conv3x3(mode, x, w, B, H, W, Cin, Cout, out=None, out_dtype=None, bias=None,
     return out
 
 
+def conv3x3_dil_live_taps(H, W, dilation):
+    """The taps ty * 3 + tx of a 3x3 kernel at this dilation that can touch an H x W map (no GPU needed)."""
+    taps = (C.c_int * 9)()
+    n = lib().segf_conv3x3_dil_live_taps(H, W, dilation, C.cast(taps, C.c_void_p))
+    if n < 0:
+        raise ValueError(f'conv3x3_dil_live_taps: bad geometry H={H} W={W} dilation={dilation}')
+    return [int(taps[i]) for i in range(n)]
+
+
+def conv3x3_dil_supported(dtype, mode, B, H, W, Cin, Cout, dilation):
+    dt = BF16 if dtype == torch.bfloat16 else (F32 if dtype == torch.float32 else -1)
+    return bool(lib().segf_conv3x3_dil_supported(dt, mode, B, H, W, Cin, Cout, dilation))
+
+
+def pick_splitk_conv3x3_dil(B, H, W, Cin, Cout, dilation):
+    return lib().segf_conv3x3_dil_pick_splitk(B, H, W, Cin, Cout, dilation)
+
+
+def conv3x3_dil(mode, x, w, B, H, W, Cin, Cout, dilation, out=None):
+    """Dilated 3x3 convolution (padding = dilation) as an implicit GEMM over the live taps, bf16 or fp32.  mode 0: y = conv(x,
+    w[Cout, 9*Cin]); mode 1: dx from (dy, wt[Cin, 9*Cout]); mode 2: dw[Cout, 9*Cin] fp32 from (x, dy).  x / w / out are 2-D views with
+    unit inner stride (column slices of wider buffers are fine)."""
+    _need_cuda(x, w)
+    assert x.dtype == w.dtype and x.stride(-1) == 1 and w.stride(-1) == 1
+    P = B * H * W
+    shape = {0: (P, Cout), 1: (P, Cin), 2: (Cout, 9 * Cin)}[mode]
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32 if mode == 2 else x.dtype, device=x.device)
+    split_k = int(lib().segf_conv3x3_dil_pick_splitk(B, H, W, Cin, Cout, dilation)) if mode == 2 else 1
+    ws = _f32(split_k * shape[0] * shape[1], x.device) if split_k > 1 else None
+    key = ('conv3x3_dil', mode, P, Cin, Cout, dilation)
+    _chk(_timed(key, lambda: lib().segf_conv3x3_dil(dt_of(x), mode, B, H, W, Cin, Cout, dilation, _ptr(x), x.stride(0), _ptr(w), w.stride(0),
+                                                    _ptr(out), out.stride(0), split_k, _ptr(ws), _stream())), 'segf_conv3x3_dil')
+    return out
+
+
+def mul_scale(x: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """y[r, c] = x[r, c] * scale[r, c]; scale fp32, contiguous (elementwise dropout and its backward)."""
+    _need_cuda(x, scale)
+    rows, cols = x.shape
+    assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == rows * cols and x.stride(1) == 1
+    y = torch.empty((rows, cols), dtype=x.dtype, device=x.device)
+    _chk(lib().segf_mul_scale(dt_of(x), _ptr(x), x.stride(0), _ptr(scale), _ptr(y), cols, rows, cols, _stream()), 'segf_mul_scale')
+    return y
+
+
 def gelu_fwd(u):
     y = torch.empty_like(u)
     _chk(lib().segf_gelu(dt_of(u), 0, _ptr(u), None, _ptr(y), u.numel(), _stream()), 'segf_gelu')

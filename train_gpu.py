@@ -64,7 +64,7 @@ def get_args_parser():
                         help='Feature extractor: MiT-B0..B5, ConvNeXt, convnextv2_{atto,femto,nano,tiny,base,large,huge}, convnext_pico, '
                              'or any name registered with segmentation_factory_amd.register_backbone')
     parser.add_argument('--pretrained_backbone', default='', type=str, metavar='MODEL')
-    parser.add_argument('--heads', default='SegFormerHead', type=str, metavar='MODEL', help='SegFormerHead | UPerHead | registered head')
+    parser.add_argument('--heads', default='SegFormerHead', type=str, metavar='MODEL', help='SegFormerHead | UPerHead | FPNHead | deeplabv3 | registered head')
     # Optimizer parameters (train_gpu.py:92-106)
     parser.add_argument('--opt', default='adamw', type=str, metavar='OPTIMIZER')
     parser.add_argument('--opt-eps', default=1e-8, type=float, metavar='EPSILON')
