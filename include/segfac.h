@@ -490,6 +490,27 @@ int segf_agc_adamw(float* param, const float* grad, float* exp_avg, float* exp_a
                    int nunits, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                    float clip_factor, float agc_eps, void* stream);
 
+/* The other --opt values of the reference's CLI (train_gpu.py:93-104: --opt / --opt-eps / --opt-betas / --momentum;
+ * train_gpu.py:269: timm.optim.create_optimizer) over the same flat buffers and unit tables as segf_agc_adamw: one launch, every
+ * hyper-parameter a launch scalar (no host read, graph-replay safe), unit_flags bit 0 = weight decay applies, bit 1 = no gradient
+ * this step (the unit is skipped entirely: no decay, no state update, no step count -- torch.optim's `p.grad is None`), per-unit
+ * step counts on the device (nullable except for SEGF_OPT_ADAM, whose bias corrections use the unit's own count).  clip_factor > 0
+ * runs the unit-wise AGC pass of segf_agc_adamw first, on the raw gradient; then g <- g + weight_decay * p (L2 coupled into the
+ * gradient) where bit 0 is set; then the rule -- the fp32 arithmetic of the torch.optim class named, maximize=False:
+ *   SEGF_OPT_SGD      torch.optim.SGD (dampening 0)      h0 = momentum, nesterov;   s0 = momentum_buffer (null when h0 == 0), s1 unused
+ *   SEGF_OPT_ADAM     torch.optim.Adam (no amsgrad)      h0 = beta1, h1 = beta2, eps;   s0 = exp_avg, s1 = exp_avg_sq
+ *   SEGF_OPT_RMSPROP  torch.optim.RMSprop (not centered) h0 = alpha, h1 = momentum, eps;  s0 = square_avg, s1 = momentum_buffer
+ *                                                         (null when h1 == 0)
+ * State buffers have the flat layout and start at zero (torch's SGD clones the first gradient into momentum_buffer, which
+ * equals momentum * 0 + g).  A null buffer the rule needs, or an unknown rule, returns SEGF_ERR_SHAPE. */
+#define SEGF_OPT_SGD 0
+#define SEGF_OPT_ADAM 1
+#define SEGF_OPT_RMSPROP 2
+int segf_flat_optim_step(int rule, float* param, const float* grad, float* s0, float* s1,
+                         const int64_t* unit_offset, const int32_t* unit_len, const uint8_t* unit_flags, int32_t* unit_step,
+                         int nunits, float lr, float weight_decay, float h0, float h1, float eps, int nesterov,
+                         float clip_factor, float agc_eps, void* stream);
+
 /* The other --clip-mode values of the reference (train_gpu.py:99-102 -> timm.utils.dispatch_clip_grad) on the flat gradient buffer:
  * mode 0 'norm' = torch.nn.utils.clip_grad_norm_(params, value, 2.0): g *= min(1, value / (||g||_2 + 1e-6));
  * mode 1 'value' = clip_grad_value_: g = clamp(g, -value, value).  ws: segf_clip_grad_ws() floats (mode 0).  No host read. */

@@ -1,4 +1,5 @@
-// Fused optimizer step over a flat fp32 parameter buffer: adaptive gradient clipping (unit-wise, AGC) + AdamW.
+// Fused optimizer steps over a flat fp32 parameter buffer: adaptive gradient clipping (unit-wise, AGC) + AdamW, and further down
+// the same structure for SGD / Adam / RMSprop (flat_optim_kernel).
 // Stands in for what engine.py:52-53 triggers through timm 0.9.2's NativeScaler: dispatch_clip_grad(mode='agc',
 // value=0.02) followed by optimizer.step() of the AdamW that create_optimizer builds (train_gpu.py:99-102,269-270).
 // timm is not installed in the build image, so this arithmetic is restated from timm 0.9.2 / torch.optim.AdamW
@@ -68,6 +69,131 @@ extern "C" int segf_agc_adamw(float* param, const float* grad, float* exp_avg, f
     const int blocks = imin((nunits + 3) / 4, 4096);
     hipLaunchKernelGGL(agc_adamw_kernel, dim3(blocks), dim3(256), 0, st, param, grad, exp_avg, exp_avg_sq, unit_offset, unit_len,
                        unit_flags, unit_step, nunits, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, clip_factor, agc_eps);
+    SEGF_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- the other --opt values of the reference's CLI (train_gpu.py:93-104 -> timm.optim.create_optimizer, train_gpu.py:269): SGD
+// (momentum / nesterov), Adam and RMSprop over the same flat buffers, unit tables, skip bit and per-unit step counts as
+// agc_adamw_kernel, so the step stays one launch with launch scalars only (graph-replay safe).  Each rule is the fp32 arithmetic of
+// the torch.optim class of that name (maximize=False, dampening 0, not centered, no amsgrad) and is pinned to it step for step:
+//   all rules:  g <- g * agc_scale (clip_factor > 0; on the RAW gradient, as dispatch_clip_grad precedes optimizer.step());
+//               g <- g + wd * p  where flag bit 0 is set (L2 coupled into the gradient)
+//   SGD:        buf <- mu buf + g;  d = g + mu buf (nesterov) | buf;  p <- p - lr d;      mu == 0: p <- p - lr g, no state
+//   ADAM:       m <- b1 m + (1-b1) g;  v <- b2 v + (1-b2) g^2;  p <- p - lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+//   RMSPROP:    sq <- a sq + (1-a) g^2;  d = g / (sqrt(sq) + eps);  mu > 0: buf <- mu buf + d, p <- p - lr buf;  else p <- p - lr d
+// torch's SGD starts momentum_buffer as a clone of the first gradient = mu * 0 + g: zero-initialised state reproduces it.
+// HBM traffic per parameter: 12 B without state, 20 B with one state buffer, 28 B with two (+ 8 B for the AGC norm pass, which
+// mostly hits L2 for units that fit).
+template <int RULE, bool MOM>
+__global__ void __launch_bounds__(256) flat_optim_kernel(float* __restrict__ param, const float* __restrict__ grad,
+                                                          float* __restrict__ s0, float* __restrict__ s1,
+                                                          const int64_t* __restrict__ unit_off, const int32_t* __restrict__ unit_len,
+                                                          const uint8_t* __restrict__ unit_flags, int32_t* __restrict__ unit_step,
+                                                          int nunits, float lr, float wd, float h0, float h1, float eps, int nesterov,
+                                                          float clip_factor, float agc_eps) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave_global = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t u = wave_global; u < nunits; u += nwaves) {
+        const int64_t off = unit_off[u];
+        const int len = unit_len[u];
+        const int uflags = unit_flags[u];
+        if (uflags & 2) continue;          // no gradient this step: torch.optim skips `p.grad is None` (no decay, no state, no count)
+        int t = 1;
+        if (unit_step) {                   // per-parameter step count, as torch keeps it (state['step']): a skipped step does not count
+            t = unit_step[u] + 1;          // every lane reads before lane 0 writes (same wave, program order)
+            if (lane == 0) unit_step[u] = t;
+        }
+        float gscale = 1.f;
+        if (clip_factor > 0.f) {           // unit-wise AGC: the arithmetic of agc_adamw_kernel
+            float pn = 0.f, gn = 0.f;
+            for (int i = lane; i < len; i += 64) {
+                const float p = param[off + i], g = grad[off + i];
+                pn = fmaf(p, p, pn); gn = fmaf(g, g, gn);
+            }
+            pn = sqrtf(wave_sum(pn)); gn = sqrtf(wave_sum(gn));
+            const float max_norm = fmaxf(pn, agc_eps) * clip_factor;
+            if (!(gn < max_norm)) gscale = max_norm / fmaxf(gn, 1e-6f);
+        }
+        const float l2 = (uflags & 1) ? wd : 0.f;
+        if (RULE == SEGF_OPT_SGD) {
+            const float mu = h0;
+            for (int i = lane; i < len; i += 64) {
+                float p = param[off + i];
+                const float g = fmaf(l2, p, grad[off + i] * gscale);
+                float d = g;
+                if (MOM) {
+                    const float buf = fmaf(mu, s0[off + i], g);
+                    s0[off + i] = buf;
+                    d = nesterov ? fmaf(mu, buf, g) : buf;
+                }
+                param[off + i] = fmaf(-lr, d, p);
+            }
+        } else if (RULE == SEGF_OPT_ADAM) {
+            const float b1 = h0, b2 = h1;
+            const float step = lr / (1.f - powf(b1, (float)t));
+            const float bc2_sqrt = sqrtf(1.f - powf(b2, (float)t));
+            for (int i = lane; i < len; i += 64) {
+                float p = param[off + i];
+                const float g = fmaf(l2, p, grad[off + i] * gscale);
+                const float mm = b1 * s0[off + i] + (1.f - b1) * g;
+                const float vv = b2 * s1[off + i] + (1.f - b2) * g * g;
+                p -= step * mm / (sqrtf(vv) / bc2_sqrt + eps);
+                param[off + i] = p; s0[off + i] = mm; s1[off + i] = vv;
+            }
+        } else {
+            const float alpha = h0, mu = h1;
+            for (int i = lane; i < len; i += 64) {
+                float p = param[off + i];
+                const float g = fmaf(l2, p, grad[off + i] * gscale);
+                const float sq = alpha * s0[off + i] + (1.f - alpha) * g * g;
+                s0[off + i] = sq;
+                float d = g / (sqrtf(sq) + eps);
+                if (MOM) {
+                    d = fmaf(mu, s1[off + i], d);
+                    s1[off + i] = d;
+                }
+                param[off + i] = fmaf(-lr, d, p);
+            }
+        }
+    }
+}
+
+extern "C" int segf_flat_optim_step(int rule, float* param, const float* grad, float* s0, float* s1, const int64_t* unit_offset,
+                                    const int32_t* unit_len, const uint8_t* unit_flags, int32_t* unit_step, int nunits, float lr,
+                                    float weight_decay, float h0, float h1, float eps, int nesterov, float clip_factor, float agc_eps,
+                                    void* stream) {
+    if (nunits <= 0) return 0;
+    if (!param || !grad || !unit_offset || !unit_len || !unit_flags) return SEGF_ERR_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = imin((nunits + 3) / 4, 4096);
+#define SEGF_FLAT_OPTIM(R, M)                                                                                                      \
+    hipLaunchKernelGGL((flat_optim_kernel<R, M>), dim3(blocks), dim3(256), 0, st, param, grad, s0, s1, unit_offset, unit_len,      \
+                       unit_flags, unit_step, nunits, lr, weight_decay, h0, h1, eps, nesterov, clip_factor, agc_eps)
+    if (rule == SEGF_OPT_SGD) {
+        if (h0 != 0.f) {
+            if (!s0) return SEGF_ERR_SHAPE;
+            SEGF_FLAT_OPTIM(SEGF_OPT_SGD, true);
+        } else {
+            if (nesterov) return SEGF_ERR_SHAPE;          // torch: "Nesterov momentum requires a momentum and zero dampening"
+            SEGF_FLAT_OPTIM(SEGF_OPT_SGD, false);
+        }
+    } else if (rule == SEGF_OPT_ADAM) {
+        if (!s0 || !s1 || !unit_step) return SEGF_ERR_SHAPE;      // the bias corrections come from the unit's own count
+        SEGF_FLAT_OPTIM(SEGF_OPT_ADAM, true);
+    } else if (rule == SEGF_OPT_RMSPROP) {
+        if (!s0) return SEGF_ERR_SHAPE;
+        if (h1 > 0.f) {
+            if (!s1) return SEGF_ERR_SHAPE;
+            SEGF_FLAT_OPTIM(SEGF_OPT_RMSPROP, true);
+        } else {
+            SEGF_FLAT_OPTIM(SEGF_OPT_RMSPROP, false);
+        }
+    } else {
+        return SEGF_ERR_SHAPE;
+    }
+#undef SEGF_FLAT_OPTIM
     SEGF_CHECK_LAUNCH();
     return 0;
 }

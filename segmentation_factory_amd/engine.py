@@ -86,13 +86,13 @@ def _graph_step_wanted(args, model, core, optimizer, loss_scaler, device):
     """The step runs as a replayed hipGraph (graph.GraphedTrainStep) unless the caller opted out.  `args.hip_graph`: True = required
     (a capture failure raises), False = eager launches, absent / None = AUTO: what `python train_gpu.py ...` as the reference's
     README launches it gets (train_gpu.py:325) -- the graph whenever the pieces it drives are the product's own (a model with
-    `forward_lowres`, the fused AGC/AdamW optimizer, the no-scaling NativeScaler) and the model is not already wrapped in
+    `forward_lowres`, one of the fused flat-buffer optimizers, the no-scaling NativeScaler) and the model is not already wrapped in
     DistributedDataParallel (whose hooks then carry the exchange); an earlier failed capture on this model keeps it eager."""
-    from .optim import FusedAGCAdamW, NativeScaler
+    from .optim import FusedFlatOptimizer, NativeScaler
     pref = getattr(args, 'hip_graph', None)
     if pref is not None and not pref:
         return False
-    ok = (hasattr(core, 'forward_lowres') and isinstance(optimizer, FusedAGCAdamW) and torch.device(device).type == 'cuda')
+    ok = (hasattr(core, 'forward_lowres') and isinstance(optimizer, FusedFlatOptimizer) and torch.device(device).type == 'cuda')
     if pref:
         return ok
     return (ok and isinstance(loss_scaler, NativeScaler) and not hasattr(model, 'module')

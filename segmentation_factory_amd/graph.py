@@ -26,7 +26,7 @@ import torch.distributed as dist
 
 from . import functional as Fh
 from . import hip
-from .optim import FusedAGCAdamW
+from .optim import FusedFlatOptimizer
 
 
 def allreduce_mean_(flat: torch.Tensor, group=None):
@@ -225,7 +225,7 @@ def sum_over_ranks_(buf, mode='all_reduce', group=None):
 
 
 class GraphedTrainStep:
-    def __init__(self, model, optimizer: FusedAGCAdamW, loss_fn, example_inputs, clip_grad=None, clip_mode='agc',
+    def __init__(self, model, optimizer: FusedFlatOptimizer, loss_fn, example_inputs, clip_grad=None, clip_mode='agc',
                  warmup: int = 2, process_group=None, bucket_mb: float = 25.0, overlap: bool = True,
                  exchange: str = None, payload: str = None, force_exchange: bool = None):
         """loss_fn(model, *inputs) -> scalar loss tensor.  ``example_inputs`` fix the shapes; their storage becomes
@@ -237,9 +237,9 @@ class GraphedTrainStep:
         changes the arithmetic, see the loss-curve test).  force_exchange: run the exchange even in a 1-rank process group
         (exercises the whole event -> communication stream -> collective -> optimizer chain on one GPU).  Environment overrides:
         SEGFAC_EXCHANGE, SEGFAC_GRAD_PAYLOAD, SEGFAC_FORCE_EXCHANGE."""
-        if not isinstance(optimizer, FusedAGCAdamW):
-            raise TypeError('GraphedTrainStep drives the fused AGC/AdamW kernel over flat buffers: pass a FusedAGCAdamW '
-                            '(create_optimizer builds one); other optimizers run on the eager path')
+        if not isinstance(optimizer, FusedFlatOptimizer):
+            raise TypeError('GraphedTrainStep drives a fused step kernel over flat buffers: pass a FusedFlatOptimizer (FusedAGCAdamW, '
+                            'FusedSGD, FusedAdam or FusedRMSprop; create_optimizer builds one); other optimizers run on the eager path')
         self.model, self.opt, self.loss_fn = model, optimizer, loss_fn
         self.static_inputs = [t.clone() for t in example_inputs]
         have_pg = dist.is_available() and dist.is_initialized()
@@ -252,7 +252,7 @@ class GraphedTrainStep:
         if force_exchange is None:
             force_exchange = bool(os.environ.get('SEGFAC_FORCE_EXCHANGE'))
         self.exchanging = have_pg and (self.world > 1 or force_exchange)
-        self.opt.set_clipping(clip_grad, clip_mode)      # 'agc' in the AdamW kernel; 'norm' / 'value' as kernels right before it
+        self.opt.set_clipping(clip_grad, clip_mode)      # 'agc' in the step kernel; 'norm' / 'value' as kernels right before it
         # parameters are re-homed into the flat buffer BEFORE capture, laid out in registration order (bucket = suffix)
         self.opt.ensure_built(order=list(model.parameters()))
         broadcast_flat_(self.opt.flat_params, 0, self.group)     # DDP's initial parameter broadcast from rank 0

@@ -1283,3 +1283,16 @@ def agc_adamw(param, grad, exp_avg, exp_avg_sq, unit_off, unit_len, unit_flags, 
     _chk(lib().segf_agc_adamw(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(unit_off), _ptr(unit_len),
                               _ptr(unit_flags), _ptr(unit_step) if unit_step is not None else None, unit_len.numel(), lr, beta1, beta2, eps, weight_decay, step, clip_factor,
                               agc_eps, _stream()), 'segf_agc_adamw')
+
+
+OPT_RULES = {'sgd': 0, 'adam': 1, 'rmsprop': 2}          # SEGF_OPT_* of include/segfac.h
+
+
+def flat_optim_step(rule, param, grad, s0, s1, unit_off, unit_len, unit_flags, unit_step, lr, weight_decay, h0, h1=0.0, eps=0.0,
+                    nesterov=False, clip_factor=0.0, agc_eps=1e-3):
+    """segf_flat_optim_step: one SGD / Adam / RMSprop step over the flat buffers (h0, h1: momentum | beta1, beta2 | alpha, momentum);
+    s0 / s1 are the rule's flat state buffers, None where it keeps none."""
+    _need_cuda(param, grad, s0, s1, unit_off, unit_len, unit_flags, unit_step)
+    _chk(lib().segf_flat_optim_step(OPT_RULES[rule], _ptr(param), _ptr(grad), _ptr(s0), _ptr(s1), _ptr(unit_off), _ptr(unit_len),
+                                    _ptr(unit_flags), _ptr(unit_step), unit_len.numel(), lr, weight_decay, h0, h1, eps,
+                                    int(bool(nesterov)), clip_factor, agc_eps, _stream()), 'segf_flat_optim_step')

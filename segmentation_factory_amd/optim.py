@@ -4,26 +4,49 @@
 timm is not available in the build image and no reference test covers this arithmetic, so AGC / AdamW are
 restated from timm 0.9.2 + torch.optim.AdamW semantics ("parity unpinned") and checked against
 the CPU restatement oracle/optim.py (tests/test_kernels_gpu.py::test_agc_adamw_known_answers).  The step itself is one HIP kernel over flat buffers.
+
+The other --opt values (train_gpu.py:93-104,269: sgd / nesterov / momentum / adam / rmsprop) run on the same flat buffers through
+segf_flat_optim_step.  Their ARITHMETIC is pinned: each rule is compared step for step with the torch.optim class of its name, which
+is installed (tests/test_optimizers_gpu.py).  The mapping from the --opt NAME to a class and its arguments is restated from timm
+0.9.2's create_optimizer_v2 and, like AGC, unpinned: timm is not available to compare against.
 """
 import torch
 
 from . import hip
 
 
-class FusedAGCAdamW(torch.optim.Optimizer):
+def _same(v):
+    return tuple(v) if isinstance(v, (list, tuple)) else v
+
+
+class FusedFlatOptimizer(torch.optim.Optimizer):
+    """What every fused optimizer of this package shares: parameters re-homed into one flat fp32 buffer (each ``p.data`` becomes a
+    view), gradients in a flat buffer of the same layout (gathered, or written in place by the backward formulas), the unit tables
+    of the step kernels (one unit = one dim-0 row of a >=2-D weight or a whole 1-D tensor), the per-step "no gradient" flags, the
+    per-unit step counts on the device, clipping in front of / inside the step, and a state_dict in the layout of the torch.optim
+    class the subclass restates (RULE).  A subclass supplies its state buffers (_state_spec) and the kernel launch (apply_flat)."""
     FLAT_SLACK = 1024        # elements of zero padding behind the flat buffers (collective ranges round up to world x 16, graph.py)
     PARAM_ALIGN = 8          # every parameter starts at a multiple of this many elements in the flat buffers (_build)
+    RULE = None              # name of the torch.optim class whose arithmetic and state_dict layout the subclass keeps
+    SHARED = ('lr',)         # hyper-parameters that are launch scalars of the one kernel: every group must agree on them
+    HAS_STEP = True          # the torch class keeps a per-parameter state['step']
+    FIXED = {}               # group entries of the torch class that the kernel supports at one value only
 
-    """AdamW whose step (optionally preceded by unit-wise adaptive gradient clipping) runs as a single
-    multi-tensor kernel (segf_agc_adamw).  Parameters are re-homed into one flat fp32 buffer (each
-    ``p.data`` becomes a view), gradients are gathered into a flat buffer of the same layout."""
-
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
         self._flat = None
         self.direct = False
         self._step = 0
         self.agc_clip = 0.0          # set per step by NativeScaler when clip_mode == 'agc'
+
+    def _state_spec(self, group):
+        """[(state_dict key, attribute holding the flat state buffer)] under the hyper-parameters of `group`."""
+        raise NotImplementedError
+
+    def _alloc_state(self):
+        for _, attr in self._state_spec(self.param_groups[0]):
+            if getattr(self, attr, None) is None:
+                setattr(self, attr, torch.zeros_like(self._flat))
 
     def _build(self, order=None):
         """order: optional sequence of parameters (e.g. ``list(model.parameters())``) that fixes the LAYOUT of the flat buffers
@@ -69,8 +92,7 @@ class FusedAGCAdamW(torch.optim.Optimizer):
             self._grad_views.append(self._grad[o:o + p.numel()].view(p.shape))
             self._offsets.append(o)
             o += span
-        self._m = torch.zeros_like(flat)
-        self._v = torch.zeros_like(flat)
+        self._alloc_state()
         self._off = torch.tensor(offs, dtype=torch.int64, device=dev)
         self._len = torch.tensor(lens, dtype=torch.int32, device=dev)
         self._flags = torch.tensor(flags, dtype=torch.uint8, device=dev)
@@ -103,7 +125,7 @@ class FusedAGCAdamW(torch.optim.Optimizer):
 
     def set_clipping(self, clip_grad, clip_mode):
         """timm.utils.dispatch_clip_grad(parameters, value=clip_grad, mode=clip_mode) as part of the optimizer step: 'agc' inside
-        the AdamW kernel, 'norm' / 'value' as kernels over the flat gradient buffer right before it (segf_clip_grad)."""
+        the step kernel, 'norm' / 'value' as kernels over the flat gradient buffer right before it (segf_clip_grad)."""
         if clip_grad is not None and clip_mode not in ('agc', 'norm', 'value'):
             raise AssertionError(f"Unknown clip mode ({clip_mode}).")          # timm's wording
         self.clip_mode = clip_mode if clip_grad is not None else 'agc'
@@ -192,28 +214,31 @@ class FusedAGCAdamW(torch.optim.Optimizer):
                 # gradient left over from an earlier step must not enter the global norm
                 torch._foreach_zero_([self._grad_views[i] for i in missing])
 
-    @torch.no_grad()
-    def apply_flat(self):
-        """AGC + AdamW over the flat buffers: one kernel launch (bias corrections are host scalars of this step)."""
-        g = self.param_groups[0]
-        # one kernel over the flat buffer: lr / betas / eps are launch scalars and weight decay is an on/off flag per unit, so
-        # every group must agree on them (timm's param_groups_weight_decay gives exactly {0, wd}); anything else would be
-        # silently ignored
+    def _launch_scalars(self):
+        """(first group, the one non-zero weight decay).  One kernel runs over the flat buffer: the hyper-parameters are launch scalars
+        and weight decay is an on/off flag per unit, so every group must agree on them (timm's param_groups_weight_decay gives exactly
+        {0, wd}); anything else would be silently ignored."""
+        g, name = self.param_groups[0], type(self).__name__
         for pg in self.param_groups[1:]:
-            if (pg['lr'], tuple(pg['betas']), pg['eps']) != (g['lr'], tuple(g['betas']), g['eps']):
-                raise NotImplementedError('FusedAGCAdamW: all parameter groups must share lr / betas / eps')
+            if any(_same(pg[k]) != _same(g[k]) for k in self.SHARED):
+                raise NotImplementedError(f'{name}: all parameter groups must share {" / ".join(self.SHARED)}')
         wds = {pg['weight_decay'] for pg in self.param_groups if pg['weight_decay'] > 0}
         if len(wds) > 1:
-            raise NotImplementedError(f'FusedAGCAdamW: one non-zero weight decay for all decayed groups, got {sorted(wds)}')
-        wd = max(pg['weight_decay'] for pg in self.param_groups)
-        self._step += 1
+            raise NotImplementedError(f'{name}: one non-zero weight decay for all decayed groups, got {sorted(wds)}')
+        return g, max(pg['weight_decay'] for pg in self.param_groups)
+
+    def _clip_front(self):
+        """Launch the 'norm' / 'value' clipping of the flat gradient buffer, if set; returns the AGC factor for the step kernel (0 = off)."""
         mode, value = getattr(self, 'clip_mode', 'agc'), getattr(self, 'clip_value', None)
         if mode in ('norm', 'value') and value is not None:      # timm dispatch_clip_grad's other modes, on the flat buffer
             if getattr(self, '_clip_ws', None) is None:
                 self._clip_ws = torch.empty(int(hip.lib().segf_clip_grad_ws()), dtype=torch.float32, device=self._grad.device)
             hip.clip_grad(self._grad, mode, value, self._clip_ws)
-        hip.agc_adamw(self._flat, self._grad, self._m, self._v, self._off, self._len, self._flags, g['lr'], g['betas'][0],
-                      g['betas'][1], g['eps'], wd, self._step, float(self.agc_clip) if mode == 'agc' else 0.0, unit_step=self._ustep)
+        return float(self.agc_clip) if mode == 'agc' else 0.0
+
+    def apply_flat(self):
+        """The step over the flat buffers: one kernel launch of the subclass's rule."""
+        raise NotImplementedError
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -229,50 +254,53 @@ class FusedAGCAdamW(torch.optim.Optimizer):
         return ids
 
     def state_dict(self):
-        """torch.optim.AdamW's state_dict layout (per-parameter 'step' / 'exp_avg' / 'exp_avg_sq' under packed indices), so the
-        checkpoint's 'optimizer_state' (train_gpu.py:354-362) can be read back by torch.optim.AdamW / timm's AdamW and vice versa."""
+        """The state_dict layout of torch.optim.<RULE> (per-parameter entries under packed indices, only for parameters that have been
+        stepped), so the checkpoint's 'optimizer_state' (train_gpu.py:354-362) can be read back by the torch class and vice versa."""
         sd = super().state_dict()
         if self._flat is not None and self._step > 0:
             ids = self._packed_ids()
+            spec = self._state_spec(self.param_groups[0])
             state = {}
-            usteps = self._ustep.cpu().tolist()
-            for i, p in enumerate(self._params):
+            usteps = self._ustep.cpu().tolist() if (spec or self.HAS_STEP) else None
+            for i, p in enumerate(self._params if usteps is not None else []):
                 n, o = p.numel(), self._offsets[i]
                 t = usteps[self._unit_range[i][0]]
                 if t > 0:                       # torch lists state only for parameters that have been stepped
-                    state[ids[id(p)]] = {'step': torch.tensor(float(t)),
-                                         'exp_avg': self._m[o:o + n].view(p.shape).detach().cpu().clone(),
-                                         'exp_avg_sq': self._v[o:o + n].view(p.shape).detach().cpu().clone()}
+                    st = {'step': torch.tensor(float(t))} if self.HAS_STEP else {}
+                    for key, attr in spec:
+                        st[key] = getattr(self, attr)[o:o + n].view(p.shape).detach().cpu().clone()
+                    state[ids[id(p)]] = st
             sd['state'] = state
         return sd
 
+    _RULE_OF_KEY = (('square_avg', 'RMSprop'), ('exp_avg', 'Adam / AdamW'), ('momentum_buffer', 'SGD'))
+
+    def _check_loadable(self, groups, state):
+        """Refuse, before anything is changed, a state_dict written by another rule: its moments would be dropped and training would
+        continue on zeroed state without a word."""
+        name = type(self).__name__
+        missing = sorted(k for k in self.defaults if any(k not in g for g in groups))
+        have = set().union(*(set(st) for st in state.values())) if state else set()
+        theirs = next((r for k, r in self._RULE_OF_KEY if k in have), None)
+        want = set() if missing else {k for k, _ in self._state_spec(groups[0])} | ({'step'} if self.HAS_STEP else set())
+        if missing or any(st and not want <= set(st) for st in state.values()):
+            raise ValueError(f'{name}.load_state_dict: this optimizer keeps torch.optim.{self.RULE} state, the state_dict holds '
+                             + (f'{theirs} state ' if theirs else '') + f'({sorted(have)} per parameter'
+                             + (f'; its groups lack {missing})' if missing else f', needed: {sorted(want)})'))
+        for g in groups:
+            for k, ok in self.FIXED.items():
+                if g.get(k) is not None and g[k] != ok:
+                    raise ValueError(f'{name}.load_state_dict: the state_dict was written with {k}={g[k]!r}; this kernel is '
+                                     f'torch.optim.{self.RULE} with {k}={ok!r}')
+
     def load_state_dict(self, sd):
-        """Accepts this class's own state_dict and a torch.optim.AdamW / timm AdamW one (the reference's checkpoints)."""
+        """Accepts this class's own state_dict and one of torch.optim.<RULE> (the reference's checkpoints)."""
         sd = dict(sd)
-        fused = sd.pop('fused', None)          # round-1 layout of this class
         state = sd.get('state', {}) or {}
+        self._check_loadable(sd['param_groups'], state)
         super().load_state_dict({'state': {}, 'param_groups': sd['param_groups']})
-        if fused and fused.get('exp_avg') is not None:
-            self.ensure_built()
-            self._step = int(fused['step'])
-            self._ustep.fill_(self._step)
-            # the round-1 layout was UNPADDED (parameters back to back); the flat buffers now align every parameter: scatter by offset
-            m_old, v_old = fused['exp_avg'].reshape(-1), fused['exp_avg_sq'].reshape(-1)
-            total = sum(p.numel() for p in self._params)
-            if m_old.numel() == self._m.numel():               # written by a build with the same (padded) layout
-                self._m.copy_(m_old)
-                self._v.copy_(v_old)
-            elif m_old.numel() == total:
-                pos = 0
-                for i, p in enumerate(self._params):
-                    n, o = p.numel(), self._offsets[i]
-                    self._m[o:o + n].copy_(m_old[pos:pos + n])
-                    self._v[o:o + n].copy_(v_old[pos:pos + n])
-                    pos += n
-            else:
-                raise ValueError(f"FusedAGCAdamW.load_state_dict: legacy 'fused' moments hold {m_old.numel()} values, the model has "
-                                 f'{total} parameters ({self._m.numel()} with alignment padding)')
-            return
+        if self._flat is not None:
+            self._alloc_state()                 # the loaded groups may switch a state buffer on (momentum 0 -> 0.9)
         if not state:
             return
         self.ensure_built()
@@ -284,16 +312,138 @@ class FusedAGCAdamW(torch.optim.Optimizer):
         for i, p in enumerate(self._params):
             offs[id(p)] = self._offsets[i]
             pos[id(p)] = i
+        spec = self._state_spec(self.param_groups[0])
         for idx, st in state.items():
             p = by_index[int(idx)]
-            if id(p) not in offs:
+            if id(p) not in offs or not st:
                 continue                        # frozen parameter: not part of the flat buffers
             o, n = offs[id(p)], p.numel()
             lo, hi = self._unit_range[pos[id(p)]]
-            self._ustep[lo:hi] = int(float(st['step']))
-            self._m[o:o + n].copy_(st['exp_avg'].reshape(-1))
-            self._v[o:o + n].copy_(st['exp_avg_sq'].reshape(-1))
-            self._step = max(self._step, int(float(st['step'])))
+            t = int(float(st['step'])) if 'step' in st else 1       # torch's SGD keeps no count: "has been stepped" is all that is known
+            self._ustep[lo:hi] = t
+            for key, attr in spec:
+                if st[key] is not None:
+                    getattr(self, attr)[o:o + n].copy_(st[key].reshape(-1))
+            self._step = max(self._step, t)
+
+
+class FusedAGCAdamW(FusedFlatOptimizer):
+    """AdamW whose step (optionally preceded by unit-wise adaptive gradient clipping) runs as a single
+    multi-tensor kernel (segf_agc_adamw).  Parameters are re-homed into one flat fp32 buffer (each
+    ``p.data`` becomes a view), gradients are gathered into a flat buffer of the same layout."""
+    RULE = 'AdamW'
+    SHARED = ('lr', 'betas', 'eps')
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def _state_spec(self, group):
+        return [('exp_avg', '_m'), ('exp_avg_sq', '_v')]
+
+    @torch.no_grad()
+    def apply_flat(self):
+        """AGC + AdamW over the flat buffers: one kernel launch (bias corrections are host scalars of this step)."""
+        g, wd = self._launch_scalars()
+        self._step += 1
+        agc = self._clip_front()
+        hip.agc_adamw(self._flat, self._grad, self._m, self._v, self._off, self._len, self._flags, g['lr'], g['betas'][0],
+                      g['betas'][1], g['eps'], wd, self._step, agc, unit_step=self._ustep)
+
+    def load_state_dict(self, sd):
+        """Accepts this class's own state_dict and a torch.optim.AdamW / timm AdamW one (the reference's checkpoints)."""
+        fused = dict(sd).get('fused', None)          # round-1 layout of this class
+        if not (fused and fused.get('exp_avg') is not None):
+            sd = dict(sd)
+            sd.pop('fused', None)
+            return super().load_state_dict(sd)
+        torch.optim.Optimizer.load_state_dict(self, {'state': {}, 'param_groups': sd['param_groups']})
+        self.ensure_built()
+        self._step = int(fused['step'])
+        self._ustep.fill_(self._step)
+        # the round-1 layout was UNPADDED (parameters back to back); the flat buffers now align every parameter: scatter by offset
+        m_old, v_old = fused['exp_avg'].reshape(-1), fused['exp_avg_sq'].reshape(-1)
+        total = sum(p.numel() for p in self._params)
+        if m_old.numel() == self._m.numel():               # written by a build with the same (padded) layout
+            self._m.copy_(m_old)
+            self._v.copy_(v_old)
+        elif m_old.numel() == total:
+            pos = 0
+            for i, p in enumerate(self._params):
+                n, o = p.numel(), self._offsets[i]
+                self._m[o:o + n].copy_(m_old[pos:pos + n])
+                self._v[o:o + n].copy_(v_old[pos:pos + n])
+                pos += n
+        else:
+            raise ValueError(f"FusedAGCAdamW.load_state_dict: legacy 'fused' moments hold {m_old.numel()} values, the model has "
+                             f'{total} parameters ({self._m.numel()} with alignment padding)')
+
+
+class _FlatRuleOptimizer(FusedFlatOptimizer):
+    """The rules of segf_flat_optim_step (csrc/optim.hip: flat_optim_kernel<RULE>)."""
+
+    @torch.no_grad()
+    def apply_flat(self):
+        g, wd = self._launch_scalars()
+        self._alloc_state()
+        self._step += 1
+        agc = self._clip_front()
+        spec = [getattr(self, attr) for _, attr in self._state_spec(g)]
+        self._launch(g, wd, agc, spec)
+
+
+class FusedSGD(_FlatRuleOptimizer):
+    """torch.optim.SGD (momentum, optional Nesterov, dampening 0, weight decay coupled into the gradient) as one kernel over the
+    flat buffers.  The momentum buffer starts at zero: torch clones the first gradient into it, which is momentum * 0 + g."""
+    RULE = 'SGD'
+    SHARED = ('lr', 'momentum', 'nesterov')
+    HAS_STEP = False
+    FIXED = {'dampening': 0, 'maximize': False}
+
+    def __init__(self, params, lr=1e-3, momentum=0, nesterov=False, weight_decay=0):
+        if nesterov and momentum <= 0:
+            raise ValueError('Nesterov momentum requires a momentum and zero dampening')          # torch's wording
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=nesterov))
+
+    def _state_spec(self, group):
+        return [('momentum_buffer', '_buf')] if group['momentum'] != 0 else []
+
+    def _launch(self, g, wd, agc, bufs):
+        hip.flat_optim_step('sgd', self._flat, self._grad, bufs[0] if bufs else None, None, self._off, self._len, self._flags,
+                            self._ustep, g['lr'], wd, h0=g['momentum'], nesterov=g['nesterov'], clip_factor=agc)
+
+
+class FusedAdam(_FlatRuleOptimizer):
+    """torch.optim.Adam: AdamW's moments with the weight decay coupled into the gradient (L2) instead of decoupled."""
+    RULE = 'Adam'
+    SHARED = ('lr', 'betas', 'eps')
+    FIXED = {'amsgrad': False, 'maximize': False, 'decoupled_weight_decay': False}
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def _state_spec(self, group):
+        return [('exp_avg', '_m'), ('exp_avg_sq', '_v')]
+
+    def _launch(self, g, wd, agc, bufs):
+        hip.flat_optim_step('adam', self._flat, self._grad, bufs[0], bufs[1], self._off, self._len, self._flags, self._ustep,
+                            g['lr'], wd, h0=g['betas'][0], h1=g['betas'][1], eps=g['eps'], clip_factor=agc)
+
+
+class FusedRMSprop(_FlatRuleOptimizer):
+    """torch.optim.RMSprop (not centered), with its optional momentum buffer."""
+    RULE = 'RMSprop'
+    SHARED = ('lr', 'alpha', 'eps', 'momentum')
+    FIXED = {'centered': False, 'maximize': False}
+
+    def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, momentum=0, weight_decay=0):
+        super().__init__(params, dict(lr=lr, alpha=alpha, eps=eps, momentum=momentum, weight_decay=weight_decay, centered=False))
+
+    def _state_spec(self, group):
+        return [('square_avg', '_sq')] + ([('momentum_buffer', '_buf')] if group['momentum'] > 0 else [])
+
+    def _launch(self, g, wd, agc, bufs):
+        hip.flat_optim_step('rmsprop', self._flat, self._grad, bufs[0], bufs[1] if len(bufs) > 1 else None, self._off, self._len,
+                            self._flags, self._ustep, g['lr'], wd, h0=g['alpha'], h1=g['momentum'], eps=g['eps'], clip_factor=agc)
 
 
 class NativeScaler:
@@ -306,10 +456,11 @@ class NativeScaler:
         loss.backward(create_graph=create_graph)
         if not need_update:
             return
-        if isinstance(optimizer, FusedAGCAdamW):
+        if isinstance(optimizer, FusedFlatOptimizer):
             optimizer.set_clipping(clip_grad, clip_mode)
         elif clip_grad is not None:
-            raise NotImplementedError('gradient clipping is fused into FusedAGCAdamW; use it or pass clip_grad=None')
+            raise NotImplementedError('gradient clipping is fused into the FusedFlatOptimizer classes (FusedAGCAdamW, FusedSGD, '
+                                      'FusedAdam, FusedRMSprop); use one of them or pass clip_grad=None')
         optimizer.step()
 
     def state_dict(self):
@@ -329,13 +480,35 @@ def param_groups_weight_decay(model, weight_decay):
     return [{'params': no_decay, 'weight_decay': 0.}, {'params': decay, 'weight_decay': weight_decay}]
 
 
+OPT_NAMES = ('adam', 'adamw', 'momentum', 'nesterov', 'rmsprop', 'sgd')
+
+
 def create_optimizer(args, model):
-    """--opt adamw path of timm.optim.create_optimizer (train_gpu.py:269) on the fused kernel."""
-    if getattr(args, 'opt', 'adamw').lower() != 'adamw':
-        raise NotImplementedError("only --opt adamw is implemented on the MI355X path")
+    """timm.optim.create_optimizer(args, model) (train_gpu.py:269) for the --opt values that have a fused kernel here: the branch of
+    timm 0.9.2's create_optimizer_v2 that each name reaches, over timm's weight-decay groups (no decay for 1-D tensors and biases).
+    The name -> class / argument mapping is restated, not pinned (timm is not installed); the arithmetic of every class is pinned to
+    torch.optim.  `sgd` IS Nesterov in timm (`momentum` is the plain form); rmsprop gets alpha=0.9; the SGD forms drop --opt-eps."""
+    opt = str(getattr(args, 'opt', 'adamw')).lower()
+    if opt not in OPT_NAMES:
+        raise NotImplementedError(f"--opt {getattr(args, 'opt', None)}: the MI355X path has fused kernels for {', '.join(OPT_NAMES)} "
+                                  "(the arithmetic of torch.optim's SGD / Adam / AdamW / RMSprop); timm's own optimizer classes are not implemented")
     wd = getattr(args, 'weight_decay', 0.025)
-    kw = dict(lr=getattr(args, 'lr', 1e-3), weight_decay=wd, eps=getattr(args, 'opt_eps', None) or 1e-8)
+    groups = param_groups_weight_decay(model, wd)
+    lr, momentum = getattr(args, 'lr', 1e-3), getattr(args, 'momentum', 0.9)
+    eps = getattr(args, 'opt_eps', None)
     betas = getattr(args, 'opt_betas', None)
+    if opt in ('sgd', 'nesterov'):
+        return FusedSGD(groups, lr=lr, momentum=momentum, nesterov=True, weight_decay=wd)
+    if opt == 'momentum':
+        return FusedSGD(groups, lr=lr, momentum=momentum, nesterov=False, weight_decay=wd)
+    if opt == 'rmsprop':
+        return FusedRMSprop(groups, lr=lr, alpha=0.9, momentum=momentum, weight_decay=wd, **({} if eps is None else {'eps': eps}))
+    if opt == 'adam':
+        kw = {} if eps is None else {'eps': eps}
+        if betas:
+            kw['betas'] = tuple(betas)
+        return FusedAdam(groups, lr=lr, weight_decay=wd, **kw)
+    kw = dict(lr=lr, weight_decay=wd, eps=eps or 1e-8)
     if betas:
         kw['betas'] = tuple(betas)
-    return FusedAGCAdamW(param_groups_weight_decay(model, wd), **kw)
+    return FusedAGCAdamW(groups, **kw)

@@ -5,8 +5,9 @@ Same flags, same epoch loop (train_one_epoch -> evaluate -> best-mIoU checkpoint
 (model_state / optimizer_state / scheduler_state / best_mIoU / F1_Score / Acc / scaler), same results / args / model
 text files, same auto-resume from the first *.pth in --save_weights_dir.  Differences, all deliberate:
 
-  * the model, loss, metrics and optimizer come from segmentation_factory_amd (HIP kernels); the optimizer is the fused
-    AGC + AdamW kernel (timm create_optimizer semantics, "parity unpinned" -- DESIGN.md);
+  * the model, loss, metrics and optimizer come from segmentation_factory_amd (HIP kernels); --opt adamw (the default) is the fused
+    AGC + AdamW kernel, --opt sgd | nesterov | momentum | adam | rmsprop (with --momentum / --opt-eps / --opt-betas) the fused
+    flat-buffer step of that rule, pinned to torch.optim (timm create_optimizer's name mapping restated, "parity unpinned" -- DESIGN.md);
   * --nb_classes / --backbone / --heads accept a superset of the reference's choices (the
     reference CLI cannot express the ADE20K-150 / ConvNeXt configurations of BASELINE.json);
   * data: the reference's `datasets` package (PIL / torchvision pipelines, out of scope here) is used unchanged when it is
@@ -66,12 +67,13 @@ def get_args_parser():
     parser.add_argument('--pretrained_backbone', default='', type=str, metavar='MODEL')
     parser.add_argument('--heads', default='SegFormerHead', type=str, metavar='MODEL', help='SegFormerHead | UPerHead | FPNHead | deeplabv3 | registered head')
     # Optimizer parameters (train_gpu.py:92-106)
-    parser.add_argument('--opt', default='adamw', type=str, metavar='OPTIMIZER')
+    parser.add_argument('--opt', default='adamw', type=str, metavar='OPTIMIZER',
+                        help='adamw | adam | sgd | nesterov (both: SGD with Nesterov momentum, as in timm) | momentum (plain SGD momentum) | rmsprop')
     parser.add_argument('--opt-eps', default=1e-8, type=float, metavar='EPSILON')
     parser.add_argument('--opt-betas', default=None, type=float, nargs='+', metavar='BETA')
     parser.add_argument('--clip-grad', type=float, default=0.02, metavar='NORM')
     parser.add_argument('--clip-mode', type=str, default='agc')
-    parser.add_argument('--momentum', type=float, default=0.9, metavar='M')
+    parser.add_argument('--momentum', type=float, default=0.9, metavar='M', help='momentum of --opt sgd / nesterov / momentum / rmsprop')
     parser.add_argument('--weight-decay', type=float, default=0.025)
     # Learning rate schedule parameters (train_gpu.py:109-146)
     parser.add_argument('--sched', default='cosine', type=str, metavar='SCHEDULER')
@@ -117,7 +119,7 @@ def get_args_parser():
     parser.add_argument('--compute-dtype', default='bf16', choices=['bf16', 'fp32'], help='activation storage (fp32 = exact-parity mode)')
     parser.add_argument('--hip-graph', dest='hip_graph', action='store_const', const=True, default=None,
                         help='REQUIRE the replayed-hipGraph train step / eval forward (a capture failure is an error).  Without either flag '
-                             'the graph is used whenever the model offers forward_lowres and the optimizer is the fused AGC/AdamW one, and '
+                             'the graph is used whenever the model offers forward_lowres and the optimizer is one of the fused flat-buffer ones (every --opt), and '
                              'a capture failure falls back to eager launches with a printed reason')
     parser.add_argument('--no-hip-graph', dest='hip_graph', action='store_const', const=False,
                         help='per-kernel (eager) launches; under several ranks the model is wrapped in DistributedDataParallel as in the reference')
