@@ -312,6 +312,26 @@ int segf_attention_bwd(int dt, int B, int heads, int N, int Nkv, int hd, const v
                        void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv,
                        float* ws, void* stream);
 
+/* ---- CrossFormer group attention core (crossformer.py:112-167, 258-339; csrc/attention_group.hip) ---------------
+ * O_g = softmax(scale Q_g K_g^T + bias[head] + keymask_g) V_g inside groups of G x G tokens of a [B, H, W] map.  Slot (gi, gj) of group
+ * (rh, rw, ih, iw) is the token at padded coordinates r = (rh G + gi) I + ih, c = (rw G + gj) I + iw, with I = interval when lda != 0 (LDA:
+ * tokens sampled at the interval) and I = 1 otherwise (SDA: adjacent tokens; interval is ignored).  Tokens with r >= H or c >= W are the
+ * reference's padding: skipped as keys, not computed as queries; groups without a real token are not launched.  G is the side the block
+ * actually uses (the caller applies the reference's small-map rule).
+ * qkv: [B H W][ldqkv], head h of q at columns h hd, of k at heads hd + h hd, of v at 2 heads hd + h hd (16-byte aligned rows);
+ * bias: [heads][G G][G G] fp32; o: [B H W][ldo] (16-byte aligned rows, as dqkv); lse: [heads][B H W] fp32 (log-sum-exp of every real query row, kept for the backward).
+ * hd = 32 and G G <= 64 only: anything else returns SEGF_ERR_SHAPE before any launch (segf_group_attention_supported answers 0).
+ * Backward: dqkv [B H W][lddqkv] receives dq | dk | dv of every real token (plain stores: each token is in exactly one group);
+ * dbias [heads][G G][G G] fp32 = dS summed over batch and groups, reduced in a fixed order through ws (segf_group_attention_bwd_ws floats):
+ * no floating-point atomics, two runs give the same bits. */
+int segf_group_attention_supported(int dt, int B, int H, int W, int heads, int hd, int G, int interval, int lda);
+int segf_group_attention_fwd(int dt, int B, int H, int W, int heads, int hd, int G, int interval, int lda, const void* qkv,
+                             int64_t ldqkv, const float* bias, float scale, void* o, int64_t ldo, float* lse, void* stream);
+int64_t segf_group_attention_bwd_ws(int B, int H, int W, int heads, int hd, int G, int interval, int lda);
+int segf_group_attention_bwd(int dt, int B, int H, int W, int heads, int hd, int G, int interval, int lda, const void* qkv,
+                             int64_t ldqkv, const float* bias, float scale, const void* d_o, int64_t lddo, const float* lse,
+                             void* dqkv, int64_t lddqkv, float* dbias, float* ws, void* stream);
+
 /* ---- depthwise 3x3 conv + bias + GELU(erf) on NHWC (mit.py:62-71,98-99 DWConv -> F.gelu) ----------- */
 int segf_dwconv3x3_gelu_fwd(int dt, int B, int H, int W, int C, const void* x, const float* w /*[C][9]*/,
                             const float* bias, int apply_gelu, void* y, void* stream);

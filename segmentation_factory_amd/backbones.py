@@ -517,3 +517,263 @@ class MobileNetV2(nn.Module):
 
     def forward(self, x):
         return [tm.nchw() for tm in self.forward_tokens(x)]
+
+
+# ---- CrossFormer (models/backbones/crossformer.py) -------------------------------------------------------------------------
+def _small_linear(x, w, b):
+    """x [T, K] W^T + b for the position-bias MLP (K <= 64, T = (2G-1)^2 rows): a broadcast multiply and a reduction, fp32."""
+    return (x.unsqueeze(1) * w.unsqueeze(0)).sum(-1) + b
+
+
+class _BiasGatherFn(torch.autograd.Function):
+    """relative_position_bias = pos[relative_position_index] as [heads, N, N] (crossformer.py:148-150).  The backward sums the
+    gradient per table row through a precomputed list of the (i, j) pairs that read the row: a gather and a reduction in a fixed
+    order, where index_select's own backward would add with floating-point atomics."""
+
+    @staticmethod
+    def forward(ctx, pos, idx, pairs, N):
+        ctx.save_for_backward(pairs)
+        ctx.N = N
+        return pos.t()[:, idx].reshape(pos.shape[1], N, N).contiguous()
+
+    @staticmethod
+    def backward(ctx, d):
+        pairs, = ctx.saved_tensors
+        heads, N = d.shape[0], ctx.N
+        dflat = torch.cat([d.reshape(heads, N * N), d.new_zeros(heads, 1)], 1)          # slot N*N: the zero the short rows point at
+        return dflat[:, pairs.reshape(-1)].reshape(heads, pairs.shape[0], pairs.shape[1]).sum(-1).t(), None, None, None
+
+
+class _PosNorm(nn.Sequential):
+    """LayerNorm -> ReLU -> Linear with the reference's keys `.0.*` / `.2.*` (crossformer.py:48-62)."""
+
+    def __init__(self, dim, out):
+        super().__init__(LayerNormWeights(dim), nn.Identity(), LinearWeights(dim, out))
+
+
+class DynamicPosBias(nn.Module):
+    """crossformer.py:36-72 with residual=False: an MLP from the (dh, dw) offset to one bias per head.  The table has (2G-1)^2 rows (169
+    for G = 7) of pos_dim <= 64 channels: it is computed once per forward per block with torch ops in fp32 on the current stream (off the
+    hot path; captured into the step's graph like everything else), and autograd carries the attention kernel's dbias back to pos.*."""
+
+    def __init__(self, dim, num_heads):
+        super().__init__()
+        self.num_heads = num_heads
+        self.pos_dim = dim // 4
+        self.pos_proj = LinearWeights(2, self.pos_dim)
+        self.pos1 = _PosNorm(self.pos_dim, self.pos_dim)
+        self.pos2 = _PosNorm(self.pos_dim, self.pos_dim)
+        self.pos3 = _PosNorm(self.pos_dim, self.num_heads)
+        self._tables = {}
+
+    def tables(self, G, device):
+        """(offsets [T, 2] fp32, relative_position_index [N*N], per-row reader lists [T, N]) of a G x G group (crossformer.py:129-144)."""
+        key = (G, str(device))
+        if key not in self._tables:
+            rng = torch.arange(1 - G, G)
+            offsets = torch.stack(torch.meshgrid([rng, rng], indexing='ij')).flatten(1).t().contiguous().float()
+            co = torch.stack(torch.meshgrid([torch.arange(G), torch.arange(G)], indexing='ij')).flatten(1)
+            rel = (co[:, :, None] - co[:, None, :]).permute(1, 2, 0).contiguous()
+            idx = ((rel[:, :, 0] + G - 1) * (2 * G - 1) + rel[:, :, 1] + G - 1).reshape(-1)
+            N, T = G * G, (2 * G - 1) ** 2
+            pairs = torch.full((T, N), N * N, dtype=torch.int64)
+            fill = [0] * T
+            for flat, t in enumerate(idx.tolist()):
+                pairs[t, fill[t]] = flat
+                fill[t] += 1
+            self._tables[key] = tuple(t.to(device) for t in (offsets, idx, pairs))
+        return self._tables[key]
+
+    def bias(self, G, device):
+        """[heads, G*G, G*G] fp32"""
+        offsets, idx, pairs = self.tables(G, device)
+        pos = _small_linear(offsets, self.pos_proj.weight, self.pos_proj.bias)
+        for m in (self.pos1, self.pos2, self.pos3):
+            pos = torch.relu(torch.nn.functional.layer_norm(pos, (self.pos_dim,), m[0].weight, m[0].bias, m[0].eps))
+            pos = _small_linear(pos, m[2].weight, m[2].bias)
+        return _BiasGatherFn.apply(pos, idx, pairs, G * G)
+
+
+class CrossFormerAttention(nn.Module):
+    """crossformer.py:82-110: parameters of the grouped attention; head dim 32 in all four variants."""
+
+    def __init__(self, dim, num_heads):
+        super().__init__()
+        assert dim == 32 * num_heads
+        self.dim, self.num_heads = dim, num_heads
+        # (quirk, :103) built as DynamicPosBias(dim // 4, ...): the module divides by 4 again, so pos_dim is dim // 16
+        self.pos = DynamicPosBias(dim // 4, num_heads)
+        self.qkv = LinearWeights(dim, dim * 3)
+        self.proj = LinearWeights(dim, dim)
+
+
+class CrossFormerMlp(nn.Module):
+    def __init__(self, dim, hidden):
+        super().__init__()
+        self.fc1 = LinearWeights(dim, hidden)
+        self.fc2 = LinearWeights(hidden, dim)
+
+
+class CrossFormerBlock(nn.Module):
+    """x + DropPath(GroupAttn(LN(x)));  x + DropPath(MLP(LN(x)))   (crossformer.py:191-352; use_acl / use_cpe off)."""
+
+    def __init__(self, dim, num_heads, group_size=7, interval=8, lsda_flag=0, dpr=0.):
+        super().__init__()
+        self.dim, self.num_heads = dim, num_heads
+        self.group_size, self.interval, self.lsda_flag = group_size, interval, lsda_flag
+        self.norm1 = LayerNormWeights(dim)
+        self.attn = CrossFormerAttention(dim, num_heads)
+        self.drop_prob = float(dpr)
+        self.norm2 = LayerNormWeights(dim)
+        self.mlp = CrossFormerMlp(dim, int(dim * 4))
+
+    def grouping(self, H, W):
+        """(group side, interval, lda) for an H x W map.  (quirk, :263-269) when min(H, W) <= group_size the block uses ONE group of side
+        max(H, W) and sets its own lsda_flag to 0 for good: module state mutated in forward, so an LDA block that has once seen a small
+        map stays in SDA mode.  Padding (:282-285) is to interval * G in LDA mode, to G in SDA mode, right and bottom only: the kernel's."""
+        if min(H, W) <= self.group_size:
+            self.lsda_flag = 0
+            G = max(H, W)
+        else:
+            G = self.group_size
+        return G, self.interval, self.lsda_flag == 1
+
+    def tokens(self, x, B, H, W, scales):
+        s1, s2 = scales
+        G, interval, lda = self.grouping(H, W)
+        x, h = Fh.layer_norm_res(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)
+        qkv = Fh.linear(h, self.attn.qkv.weight, self.attn.qkv.bias)
+        bias = self.attn.pos.bias(G, x.device)
+        o = Fh.group_attention(qkv, bias, B, H, W, self.num_heads, G, interval, lda)
+        x = Fh.linear(o, self.attn.proj.weight, self.attn.proj.bias, residual=x, rscale=s1, rows_per_group=H * W)
+        x, h = Fh.layer_norm_res(x, self.norm2.weight, self.norm2.bias, self.norm2.eps)
+        f = Fh.gelu(Fh.linear(h, self.mlp.fc1.weight, self.mlp.fc1.bias))
+        return Fh.linear(f, self.mlp.fc2.weight, self.mlp.fc2.bias, residual=x, rscale=s2, rows_per_group=H * W)
+
+
+class CrossFormerPatchEmbed(nn.Module):
+    """crossformer.py:532-582 with patch_size=[4]: one conv k4 s4 p0 + LayerNorm."""
+
+    def __init__(self, embed_dim):
+        super().__init__()
+        self.projs = nn.ModuleList([ConvWeights(3, embed_dim, 4, 4, 0)])
+        self.norm = LayerNormWeights(embed_dim)
+
+
+class CrossFormerPatchMerging(nn.Module):
+    """crossformer.py:380-423 with patch_size=[2]: LayerNorm + one conv k2 s2 p0 to twice the width."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.reductions = nn.ModuleList([ConvWeights(dim, 2 * dim, 2, 2, 0)])
+        self.norm = LayerNormWeights(dim)
+
+
+class CrossFormerStage(nn.Module):
+    def __init__(self, dim, depth, num_heads, group_size, interval, dprs, downsample):
+        super().__init__()
+        # even blocks SDA, odd blocks LDA (:475)
+        self.blocks = nn.ModuleList([CrossFormerBlock(dim, num_heads, group_size, interval, i % 2, dprs[i]) for i in range(depth)])
+        self.downsample = CrossFormerPatchMerging(dim) if downsample else None
+
+
+class CrossFormer(nn.Module):
+    """models/backbones/crossformer.py:598-782 as its four factories build it: patch_size [4], merge_size [[2], [2], [2]], group size 7,
+    intervals [8, 4, 2, 1], mlp ratio 4, drop-path rates linspace(0, 0.1, sum(depths)); ape, use_cpe and use_acl off.  The stage outputs
+    go to the decode head as they are (no output norm)."""
+
+    def __init__(self, embed_dim=96, depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), group_size=(7, 7, 7, 7), crs_interval=(8, 4, 2, 1),
+                 drop_path_rate=0.1):
+        super().__init__()
+        self.channels = [embed_dim, embed_dim * 2, embed_dim * 4, embed_dim * 8]
+        self.depths = list(depths)
+        self.compute_dtype = torch.bfloat16
+        self.stochastic_override = None      # tests: {'drop_path': keep[n_draws, B]}
+        self.patch_embed = CrossFormerPatchEmbed(embed_dim)
+        dpr = [x.item() for x in torch.linspace(0, drop_path_rate, sum(depths))]
+        self.layers = nn.ModuleList()
+        for i in range(4):
+            self.layers.append(CrossFormerStage(embed_dim * 2 ** i, depths[i], num_heads[i], group_size[i], crs_interval[i],
+                                                dpr[sum(depths[:i]):sum(depths[:i + 1])], i < 3))
+        self.apply(self._init_weights)
+
+    @staticmethod
+    def _init_weights(m):
+        """crossformer.py:749-758: trunc_normal(.02) on Linear weights, LayerNorm at 1 / 0; Linear biases and the Conv2d weights of
+        patch_embed.projs / downsample.reductions keep torch's default initialisation."""
+        from .containers import trunc_normal_
+        if isinstance(m, nn.Linear):
+            trunc_normal_(m.weight, std=.02)
+        elif isinstance(m, nn.LayerNorm):
+            nn.init.constant_(m.bias, 0)
+            nn.init.constant_(m.weight, 1.0)
+
+    def _blocks(self):
+        return [blk for st in self.layers for blk in st.blocks]
+
+    def _drop_path_scales(self, B, device):
+        """One (attention, mlp) pair of [B] keep / kp scale rows per block with rate > 0: the block's one DropPath module is applied
+        twice (:342-343); rate-0 blocks are nn.Identity in the reference and draw nothing."""
+        rates = [blk.drop_prob for blk in self._blocks()]
+        if not self.training or all(r == 0 for r in rates):
+            return [(None, None)] * len(rates)
+        draws = [r for r in rates if r > 0 for _ in range(2)]
+        if self.stochastic_override is not None and 'drop_path' in self.stochastic_override:
+            kp = 1.0 - torch.tensor(draws, dtype=torch.float32, device=device)[:, None]
+            scale = (self.stochastic_override['drop_path'].to(device=device, dtype=torch.float32) / kp).contiguous()
+        else:
+            scale = Fh.stochastic_scales(self, tuple(1.0 - r for r in draws), B, device)
+        out, i = [], 0
+        for r in rates:
+            if r > 0:
+                out.append((scale[i], scale[i + 1]))
+                i += 2
+            else:
+                out.append((None, None))
+        return out
+
+    def forward_tokens(self, x):
+        """x: fp32 NCHW image.  Returns 4 TokenMaps (strides 4/8/16/32)."""
+        B, _, H, W = x.shape
+        dtype = self.compute_dtype
+        scales = self._drop_path_scales(B, x.device)
+        pe = self.patch_embed
+        t = Fh.conv_patch(x, pe.projs[0].weight, pe.projs[0].bias, (B, H, W, 3, 4, 4, 0), image=True, dtype=dtype)
+        H, W = (H - 4) // 4 + 1, (W - 4) // 4 + 1
+        t = Fh.layer_norm(t, pe.norm.weight, pe.norm.bias, pe.norm.eps)
+        outs, bi = [], 0
+        for i, st in enumerate(self.layers):
+            for blk in st.blocks:
+                t = blk.tokens(t, B, H, W, scales[bi])
+                bi += 1
+            if st.downsample is None:
+                outs.append(TokenMap(t, B, H, W))
+                break
+            t, th = Fh.fork(t, 2)                    # the stage output feeds the decode head and the patch merging
+            outs.append(TokenMap(th, B, H, W))
+            ds = st.downsample
+            assert H % 2 == 0 and W % 2 == 0, f"x size ({H}*{W}) are not even."
+            t = Fh.layer_norm(t, ds.norm.weight, ds.norm.bias, ds.norm.eps)
+            t = Fh.conv_patch(t, ds.reductions[0].weight, ds.reductions[0].bias, (B, H, W, self.channels[i], 2, 2, 0))
+            H, W = H // 2, W // 2
+        return outs
+
+    def forward(self, x):
+        return [tm.nchw() for tm in self.forward_tokens(x)]
+
+
+# the reference's factories (crossformer.py:785-825)
+def crossformer_tiny(**kw):
+    return CrossFormer(embed_dim=64, depths=[1, 1, 8, 6], num_heads=[2, 4, 8, 16], **kw)
+
+
+def crossformer_small(**kw):
+    return CrossFormer(embed_dim=96, depths=[2, 2, 6, 2], num_heads=[3, 6, 12, 24], **kw)
+
+
+def crossformer_base(**kw):
+    return CrossFormer(embed_dim=96, depths=[2, 2, 18, 2], num_heads=[3, 6, 12, 24], **kw)
+
+
+def crossformer_large(**kw):
+    return CrossFormer(embed_dim=128, depths=[2, 2, 18, 2], num_heads=[4, 8, 16, 32], **kw)

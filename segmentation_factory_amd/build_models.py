@@ -20,7 +20,7 @@ backbone_registry = {'MiT': _backbones.MiT, 'ConvNeXt': _backbones.ConvNeXt, 'Co
                      'MobileNetV2': _backbones.MobileNetV2}
 backbone_registry.update({n: getattr(_backbones, n) for n in (
     'convnextv2_atto', 'convnextv2_femto', 'convnext_pico', 'convnextv2_nano', 'convnextv2_tiny', 'convnextv2_base',
-    'convnextv2_large', 'convnextv2_huge')})
+    'convnextv2_large', 'convnextv2_huge', 'crossformer_tiny', 'crossformer_small', 'crossformer_base', 'crossformer_large')})
 head_dict = {'SegFormerHead': _heads.SegFormerHead, 'UPerHead': _heads.UPerHead, 'FPNHead': _heads.FPNHead}
 
 

@@ -857,6 +857,60 @@ def attention(q, kv, B, N, Nkv, heads):
     return AttentionFn.apply(q, kv, B, N, Nkv, heads)
 
 
+def group_token_index(H, W, G, interval, lda):
+    """[groups, G*G] int64: for every (group, slot) of CrossFormer's SDA (lda false: adjacent tokens) or LDA (tokens sampled at
+    `interval`) grouping of an H x W map, the flat token index r * W + c, or -1 where the slot is padding (crossformer.py:282-313: the map
+    is padded on the right and bottom to a multiple of G, of interval * G in LDA mode).  Groups in the reference's order, groups that
+    are all padding included.  Pure Python on the CPU: it pins the map the kernel computes for itself (csrc/attention_group.hip never
+    reads it)."""
+    I = int(interval) if lda else 1
+    div = G * I
+    Rh, Rw = -(-H // div), -(-W // div)
+    out = torch.full((Rh * Rw * I * I, G * G), -1, dtype=torch.int64)
+    for rh in range(Rh):
+        for rw in range(Rw):
+            for ih in range(I):
+                for iw in range(I):
+                    g = ((rh * Rw + rw) * I + ih) * I + iw
+                    for gi in range(G):
+                        r = (rh * G + gi) * I + ih
+                        if r >= H:
+                            continue
+                        for gj in range(G):
+                            c = (rw * G + gj) * I + iw
+                            if c < W:
+                                out[g, gi * G + gj] = r * W + c
+    return out
+
+
+class GroupAttentionFn(Function):
+    """CrossFormer's attention core (crossformer.py:121-164 inside the grouping of :282-339): per group of G x G tokens and head,
+    softmax(scale q k^T + bias[head] + key mask) v, on the qkv Linear's [B*H*W, 3C] output as it lies; o in token order.  Gradients go to
+    qkv and to the [heads, G*G, G*G] bias."""
+
+    @staticmethod
+    def forward(ctx, qkv, bias, B, H, W, heads, G, interval, lda):
+        qkv = _rowmajor(qkv)
+        bias = bias.detach().contiguous()
+        scale = 32 ** -0.5
+        o, lse = hip.group_attention_fwd(qkv, bias, B, H, W, heads, G, interval, lda, scale)
+        ctx.save_for_backward(qkv, bias, lse)
+        ctx.meta = (B, H, W, heads, G, interval, lda, scale)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, bias, lse = ctx.saved_tensors
+        B, H, W, heads, G, interval, lda, scale = ctx.meta
+        dqkv, dbias = hip.group_attention_bwd(qkv, bias, _rowmajor(do), lse, B, H, W, heads, G, interval, lda, scale)
+        return dqkv, dbias, None, None, None, None, None, None, None
+
+
+def group_attention(qkv, bias, B, H, W, heads, G, interval, lda):
+    """G: the group side in use (after the reference's small-map rule); head dim 32."""
+    return GroupAttentionFn.apply(qkv, bias, B, H, W, heads, G, interval, bool(lda))
+
+
 @direct_grads(1, 2)
 class DWConvGeluFn(Function):
     """gelu(depthwise3x3(x) + b) on NHWC tokens (mit.py:62-71 + F.gelu at :99)."""

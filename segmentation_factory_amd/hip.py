@@ -913,6 +913,46 @@ def attention_bwd(q, k, v, o, d_o, lse, B, heads, N, Nkv, hd, scale, dk, dv):
     return dq
 
 
+def _group_attention_check(t, B, H, W, heads, G, interval, lda):
+    """The refusal happens here, on the host, before any launch: head dim 32 and G * G <= 64 slots per group only."""
+    if G * G <= 64 and not lib().segf_group_attention_supported(dt_of(t), B, H, W, heads, 32, G, interval, int(lda)):
+        raise RuntimeError(f'group attention: no kernel for a {H} x {W} map, batch {B}, {heads} heads of 32, groups of {G} x {G} '
+                           f'({"LDA" if lda else "SDA"}, interval {interval}): sizes must be positive and B * H * W below 2^29')
+    if G * G > 64:
+        raise RuntimeError(f'group attention: no kernel for groups of {G} x {G} = {G * G} tokens ({"LDA" if lda else "SDA"}, interval '
+                           f'{interval}) on a {H} x {W} map, batch {B}, {heads} heads of 32: a group holds at most 64 tokens '
+                           f'(there is no fallback path)')
+
+
+def group_attention_fwd(qkv, bias, B, H, W, heads, G, interval, lda, scale):
+    """qkv: [B*H*W, >= 3*heads*32] view (unit inner stride) = [q | k | v]; bias: [heads, G*G, G*G] fp32.  -> (o [B*H*W, heads*32], lse)."""
+    _need_cuda(qkv, bias)
+    _group_attention_check(qkv, B, H, W, heads, G, interval, lda)
+    rows = B * H * W
+    assert qkv.shape[0] == rows and qkv.stride(1) == 1 and bias.is_contiguous() and bias.dtype == torch.float32
+    assert qkv.shape[1] >= 3 * heads * 32, f'qkv has {qkv.shape[1]} columns, {heads} heads of 32 need {3 * heads * 32}'
+    assert tuple(bias.shape) == (heads, G * G, G * G), (tuple(bias.shape), heads, G)
+    o = torch.empty((rows, heads * 32), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty((heads, rows), dtype=torch.float32, device=qkv.device)
+    _chk(lib().segf_group_attention_fwd(dt_of(qkv), B, H, W, heads, 32, G, interval, int(lda), _ptr(qkv), qkv.stride(0), _ptr(bias),
+                                        scale, _ptr(o), o.stride(0), _ptr(lse), _stream()), 'segf_group_attention_fwd')
+    return o, lse
+
+
+def group_attention_bwd(qkv, bias, d_o, lse, B, H, W, heads, G, interval, lda, scale):
+    """-> (dqkv [B*H*W, 3*heads*32] in qkv's dtype, dbias [heads, G*G, G*G] fp32)."""
+    _need_cuda(qkv, bias, d_o)
+    _group_attention_check(qkv, B, H, W, heads, G, interval, lda)
+    assert qkv.shape[1] >= 3 * heads * 32 and d_o.shape[1] >= heads * 32 and d_o.stride(1) == 1
+    dqkv = torch.empty((B * H * W, 3 * heads * 32), dtype=qkv.dtype, device=qkv.device)
+    dbias = torch.empty((heads, G * G, G * G), dtype=torch.float32, device=qkv.device)
+    ws = _f32(lib().segf_group_attention_bwd_ws(B, H, W, heads, 32, G, interval, int(lda)), qkv.device)
+    _chk(lib().segf_group_attention_bwd(dt_of(qkv), B, H, W, heads, 32, G, interval, int(lda), _ptr(qkv), qkv.stride(0), _ptr(bias),
+                                        scale, _ptr(d_o), d_o.stride(0), _ptr(lse), _ptr(dqkv), dqkv.stride(0), _ptr(dbias), _ptr(ws),
+                                        _stream()), 'segf_group_attention_bwd')
+    return dqkv, dbias
+
+
 # ---- spatial ----------------------------------------------------------------------------------------
 def dwconv3x3_gelu_fwd(x, w9, bias, B, H, W, Cc, apply_gelu=True):
     y = torch.empty_like(x)

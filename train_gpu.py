@@ -63,6 +63,7 @@ def get_args_parser():
     # Model parameters (train_gpu.py:76-90)
     parser.add_argument('--backbone', default='MiT-B2', type=str, metavar='MODEL',
                         help='Feature extractor: MiT-B0..B5, ConvNeXt, convnextv2_{atto,femto,nano,tiny,base,large,huge}, convnext_pico, '
+                             'crossformer_{tiny,small,base,large}, '
                              'or any name registered with segmentation_factory_amd.register_backbone')
     parser.add_argument('--pretrained_backbone', default='', type=str, metavar='MODEL')
     parser.add_argument('--heads', default='SegFormerHead', type=str, metavar='MODEL', help='SegFormerHead | UPerHead | FPNHead | deeplabv3 | registered head')
