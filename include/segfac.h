@@ -342,6 +342,16 @@ int segf_dwconv3x3_bwd_blocks(int dt, int B, int H, int W, int C);
 int segf_dwconv3x3_gelu_bwd(int dt, int B, int H, int W, int C, const void* x, const float* w, const float* bias,
                             int apply_gelu, const void* dy, void* du, void* dx, float* dw, float* db,
                             float* ws, void* stream);
+/* Mix-FFN backward (mit.py:98-99: fc2(gelu(dwconv(f)))) without the hidden-width gradient map: dg = dys W2 is formed inside pass A,
+ * du = dg * gelu'(conv(f)+b), then dx / dw / db as above (same ws, same deferred finalize with dw == NULL).  Only for maps whose
+ * segf_dwconv3x3_gelu_bwd runs the three walk passes (not the one-launch form of small maps, not SEGFAC_DW_NO_WALK): others are refused.
+ * bf16 only; C_in = 32 or 64, C_hidden % 64 == 0; dys [B H W][C_in] with row stride ld_dys (elements, % 8 == 0); w2 bf16
+ * [C_in][C_hidden] as layout-1 segf_gemm takes it.  Results carry the bits of segf_gemm(layout 1) + segf_dwconv3x3_gelu_bwd.
+ * _supported: host arithmetic only; the shape rule, the walk form in use, and SEGFAC_FFN_BWD_FUSED (0 never, 1 by size, 2 always). */
+int segf_dwconv3x3_gelu_bwd_fc2_supported(int dt, int B, int H, int W, int C_hidden, int C_in);
+int segf_dwconv3x3_gelu_bwd_fc2(int dt, int B, int H, int W, int C_hidden, int C_in, const void* f, const float* w9,
+                                const float* bias, const void* dys, int64_t ld_dys, const void* w2, void* du, void* dx,
+                                float* dw, float* db, float* ws, void* stream);
 
 /* ---- depthwise 7x7 conv + bias on NHWC (ConvNeXt Block.dwconv, convnext.py:29,39; convnextv2.py:88,101) --------------
  * wt: fp32 [49][C] (the [C][1][7][7] parameter transposed with segf_permute021); C % 8 == 0.                    */
@@ -622,6 +632,7 @@ int segf_input_val(const uint8_t* img, int64_t img_stride, const uint8_t* lbl, i
  *   SEGFAC_DW_WALK_ROWS          depthwise 3 x 3 walk: rows per segment (0 = chosen from the map size)
  *   SEGFAC_DW_NO_SMALL           depthwise 3 x 3 backward of small maps: three passes instead of the one-launch LDS form
  *   SEGFAC_DW_SMALL_ALWAYS       ... the one-launch form beyond one round of workgroups as well
+ *   SEGFAC_FFN_BWD_FUSED         Mix-FFN backward, fc2's data gradient formed inside pass A of the depthwise backward (segf_dwconv3x3_gelu_bwd_fc2_supported): 0 = never, 1 = from 131072 token rows on, 2 = wherever the shape has the kernel  (default 1)
  *   SEGFAC_NO_FUSE_MAP           folded SegFormerHead map: streaming product + VALU upsample-add instead of fuse_map_kernel
  *   SEGFAC_NO_BWD248_MFMA        transposed 1/2-1/4-1/8 resizes on the VALU kernel instead of fuse_map_bwd_kernel
  *   SEGFAC_UPADD_GENERIC         upsample-add: the generic per-source kernels also for the 2-4-8 pyramid

@@ -106,6 +106,10 @@ class MLP(nn.Module):
 
     def tokens(self, h, B, H, W, residual, rscale):
         f = Fh.linear(h, self.fc1.weight, self.fc1.bias)
+        dw = self.dwconv.dwconv
+        if Fh.dwconv3x3_gelu_linear_ok(f, self.fc2.weight, self.fc2.bias, dw.weight, dw.bias, B, H, W):
+            # large maps: one formula for dwconv + GELU -> fc2, whose backward never stores fc2's hidden-width data gradient
+            return Fh.dwconv3x3_gelu_linear(f, self.fc2.weight, self.fc2.bias, dw.weight, dw.bias, B, H, W, residual=residual, rscale=rscale)
         g = Fh.dwconv3x3_gelu(f, self.dwconv.dwconv.weight, self.dwconv.dwconv.bias, B, H, W, True)
         return Fh.linear(g, self.fc2.weight, self.fc2.bias, residual=residual, rscale=rscale, rows_per_group=H * W)
 

@@ -272,6 +272,163 @@ static inline void dw_walk_launch(hipStream_t st, const T* x, const float* w, co
     hipLaunchKernelGGL((dwconv3x3_walk_kernel<T, MODE>), dim3(blocks), dim3(256), 0, st, x, w, bias, apply_gelu, dy, y, B, H, W, C, R, nseg);
 }
 
+// ---- backward pass A of Mix-FFN with fc2's data gradient formed in place (mit.py:98-99 backward) ---------------------------------
+// dwconv3x3_walk_kernel<bf16, 2> whose gradient rows dg = dys W2 (thin K = C_in = 32 KS) never exist in memory: a WAVE owns a 16-pixel
+// run along W x 64 hidden channels and walks down its row segment; the 16 dys token rows of an image row ARE the MFMA A operand as
+// they lie in memory (lane (i = l & 15, g = l >> 4) loads the 16 bytes dys[pixel i][32 s + 8 g ..]), the B operands are W2 fragments
+// kept in registers with their columns dealt so that MFMA j, column n is hidden channel 4 n + j: after the four products lane (n, g)
+// holds pixels 4 g .. 4 g + 3 x channels 4 n .. 4 n + 3, the 4 x 4 ownership of the walk kernel.  Per output element the product is
+// the instruction sequence of gemm_skinny_kernel (accumulator from zero, K steps of 32 ascending, one rounding to bf16), so du has
+// the bits of the two-launch form.  The f loads of the 16 lanes of a group cover 128 contiguous bytes per pixel.
+// The column set-up, the row rotation, the 3 x 3 scatter and the GELU / store tail are those of dwconv3x3_walk_kernel<T, 2> line for line: a fix to
+// the walk (the vy / segment-seam logic, say) belongs in both.  (Shared __forceinline__ helpers changed the register allocation of the existing walk
+// kernels when tried, so folding the two bodies together goes with a re-measurement of those kernels.)
+typedef __attribute__((ext_vector_type(8))) __bf16 dwf_bf16x8;
+typedef __attribute__((ext_vector_type(4))) float dwf_f32x4;
+typedef __attribute__((ext_vector_type(8))) short dwf_s16x8;
+typedef uint32_t dwf_u32x4 __attribute__((ext_vector_type(4)));
+template <int KS>
+__global__ void __launch_bounds__(256, 2) dwconv3x3_walk_fc2_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w,
+                                                                     const float* __restrict__ bias, const bf16_t* __restrict__ dys,
+                                                                     int64_t ld_dys, const bf16_t* __restrict__ w2,
+                                                                     bf16_t* __restrict__ y, int B, int H, int W, int C, int R, int nseg) {
+    typedef bf16_t T;
+    const int lane = threadIdx.x & 63;
+    const int n = lane & 15, g = lane >> 4;
+    const int nslab = C / 64;
+    const int nrun = (W + 15) / 16;
+    const int units = B * nseg * nrun;
+    // wave-uniform bookkeeping lives in scalar registers
+    const int wv = __builtin_amdgcn_readfirstlane((int)(xcd_block() * 4 + (threadIdx.x >> 6)));
+    const int ustep = (int)((gridDim.x * 4) / nslab);              // the launch makes the wave count a multiple of nslab
+    const int cbase = (wv % nslab) * 64;
+    const int c0 = cbase + 4 * n;
+    f32x2_t wk[9][2], bs[2];
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+#pragma unroll
+        for (int kk = 0; kk < 9; ++kk) wk[kk][jj] = f32x2_t{w[(c0 + 2 * jj) * 9 + kk], w[(c0 + 2 * jj + 1) * 9 + kk]};
+        bs[jj] = bias ? f32x2_t{bias[c0 + 2 * jj], bias[c0 + 2 * jj + 1]} : f32x2_t{0.f, 0.f};
+    }
+    // W2 fragments: Bf[j][s] element e = w2[32 s + 8 g + e][c0 + j]
+    dwf_bf16x8 Bf[4][KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        dwf_s16x8 t[4];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const uint2 q = *reinterpret_cast<const uint2*>(w2 + (int64_t)(32 * s + 8 * g + e) * C + c0);
+            t[0][e] = (short)(q.x & 0xffffu); t[1][e] = (short)(q.x >> 16); t[2][e] = (short)(q.y & 0xffffu); t[3][e] = (short)(q.y >> 16);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) Bf[j][s] = __builtin_bit_cast(dwf_bf16x8, t[j]);
+    }
+    const int steps = (R + 2 + 2) / 3;
+    for (int u = wv / nslab; u < units; u += ustep) {
+        const int run = u % nrun;
+        const int t = u / nrun;
+        const int seg = t % nseg;
+        const int b = t / nseg;
+        const int x0 = run * 16 + 4 * g;
+        const int ya = seg * R, yb = ya + R < H ? ya + R : H;
+        const T* xb = x + (int64_t)b * H * W * C + c0;
+        T* yo_b = y + (int64_t)b * H * W * C + c0;
+        // this lane's dys token of an image row (A operand row n), clamped into the row: pixels past W are never stored
+        const int tpx = run * 16 + n < W ? run * 16 + n : W - 1;
+        const T* gb = dys + ((int64_t)b * H * W + tpx) * ld_dys + 8 * g;
+        int coff[DW_PIX + 2];
+        bool cok[DW_PIX + 2];
+#pragma unroll
+        for (int cx = 0; cx < DW_PIX + 2; ++cx) {
+            const int ix = x0 + cx - 1;
+            cok[cx] = ix >= 0 && ix < W;
+            coff[cx] = (ix < 0 ? 0 : (ix >= W ? W - 1 : ix)) * C;
+        }
+        f32x2_t acc[3][DW_PIX][2];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int p = 0; p < DW_PIX; ++p) { acc[a][p][0] = bs[0]; acc[a][p][1] = bs[1]; }
+        Raw4<T> rawb[3][DW_PIX + 2];
+        dwf_u32x4 dysb[3][KS];                                    // rotating like the input rows: two rows ahead of their use
+        auto load_row = [&](int yin, Raw4<T> (&dst)[DW_PIX + 2]) {
+            const int yc = yin < 0 ? 0 : (yin >= H ? H - 1 : yin);
+            const T* row = xb + (int64_t)yc * W * C;
+#pragma unroll
+            for (int cx = 0; cx < DW_PIX + 2; ++cx) dst[cx] = load4_raw<T>(row + coff[cx]);
+        };
+        auto load_grow = [&](int yo, dwf_u32x4 (&dst)[KS]) {
+            const int yc = yo < 0 ? 0 : (yo >= H ? H - 1 : yo);
+            const T* row = gb + (int64_t)yc * W * ld_dys;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) dst[s] = *reinterpret_cast<const dwf_u32x4*>(row + 32 * s);
+        };
+        load_row(ya - 1, rawb[0]);
+        load_row(ya, rawb[1]);
+        load_grow(ya - 2, dysb[0]); load_grow(ya - 1, dysb[1]);
+        int yin = ya - 1;
+        for (int st = 0; st < steps; ++st) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j, ++yin) {
+                f32x2_t (&P)[DW_PIX][2] = acc[j % 3];
+                f32x2_t (&Cc)[DW_PIX][2] = acc[(j + 1) % 3];
+                f32x2_t (&N)[DW_PIX][2] = acc[(j + 2) % 3];
+                Raw4<T> (&curc)[DW_PIX + 2] = rawb[j % 3];                // input row yin (loaded two sub-steps ago)
+                dwf_u32x4 (&gcurc)[KS] = dysb[j % 3];                     // dys row yin - 1
+                load_row(yin + 2, rawb[(j + 2) % 3]);
+                load_grow(yin + 1, dysb[(j + 2) % 3]);
+                const bool vy = yin >= 0 && yin < H && yin <= yb;
+#pragma unroll
+                for (int cx = 0; cx < DW_PIX + 2; ++cx) {
+                    f32x2_t v[2];
+                    unpack4v(curc[cx], vy && cok[cx], v);
+#pragma unroll
+                    for (int kx = 0; kx < 3; ++kx) {
+                        const int p = cx - kx;
+                        if (p >= 0 && p < DW_PIX) {
+#pragma unroll
+                            for (int jj = 0; jj < 2; ++jj) {
+                                P[p][jj] = wk[6 + kx][jj] * v[jj] + P[p][jj];
+                                Cc[p][jj] = wk[3 + kx][jj] * v[jj] + Cc[p][jj];
+                                N[p][jj] = wk[kx][jj] * v[jj] + N[p][jj];
+                            }
+                        }
+                    }
+                }
+                const int yo = yin - 1;
+                if (yo >= ya && yo < yb) {                                // wave-uniform
+                    // dg of row yo: element r of product j = pixel 4 g + r, channel c0 + j
+                    dwf_f32x4 dgf[4];
+#pragma unroll
+                    for (int jm = 0; jm < 4; ++jm) {
+                        dgf[jm] = dwf_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                        for (int s = 0; s < KS; ++s)
+                            dgf[jm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(dwf_bf16x8, gcurc[s]), Bf[jm][s], dgf[jm], 0, 0, 0);
+                    }
+                    T* orow = yo_b + (int64_t)yo * W * C;
+#pragma unroll
+                    for (int h = 0; h < DW_PIX / 2; ++h) {
+                        f32x2_t a8[4] = {P[2 * h][0], P[2 * h][1], P[2 * h + 1][0], P[2 * h + 1][1]};
+                        Raw4<T> q0, q1;                                   // the bf16 rounding the stored dg had
+                        q0.u.x = pack2bf(dgf[0][2 * h], dgf[1][2 * h]); q0.u.y = pack2bf(dgf[2][2 * h], dgf[3][2 * h]);
+                        q1.u.x = pack2bf(dgf[0][2 * h + 1], dgf[1][2 * h + 1]); q1.u.y = pack2bf(dgf[2][2 * h + 1], dgf[3][2 * h + 1]);
+                        f32x2_t gy[4], g0[2], g1[2];
+                        unpack4v(q0, true, g0); unpack4v(q1, true, g1);
+                        gy[0] = g0[0]; gy[1] = g0[1]; gy[2] = g1[0]; gy[3] = g1[1];
+                        gelu_erf8<true>(a8, gy);
+                        const f32x2_t o0[2] = {a8[0], a8[1]}, o1[2] = {a8[2], a8[3]};
+                        if (cok[2 * h + 1]) store4v(orow + coff[2 * h + 1], o0);
+                        if (cok[2 * h + 2]) store4v(orow + coff[2 * h + 2], o1);
+                    }
+                }
+#pragma unroll
+                for (int p = 0; p < DW_PIX; ++p) { P[p][0] = bs[0]; P[p][1] = bs[1]; }
+            }
+        }
+    }
+}
+
 static inline int dw_blocks(int B, int H, int W, int C) {
     // 8 strips per thread: the 72 per-channel weights a thread keeps in registers are loaded once per 8 strips
     return colfixed_blocks((int64_t)B * H * ((W + DW_PIX - 1) / DW_PIX), C / 8, 8, 16384);
@@ -762,6 +919,63 @@ extern "C" int segf_dwconv3x3_bwd_blocks(int dt, int B, int H, int W, int C) {
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
     if (dw_small_nch(dt, B, H, W, C)) return B;
     return dw_use_walk() ? dww_plan(B, H, W, C).nblk : dwg_plan(B, H, W, C).nblk;
+}
+
+// Mix-FFN backward with fc2's data gradient formed inside pass A (dwconv3x3_walk_fc2_kernel); passes B and C are the unchanged walk
+// kernels, the workspace and the deferred finalize (dw == NULL) are those of segf_dwconv3x3_gelu_bwd in its walk form.
+// Token rows from which policy value 1 takes the fused form (tools/bench_ffn_bwd.py, profiles/ffn_bwd_fused_ab.jsonl).
+#define DW_FC2_MIN_ROWS 131072
+static inline bool dw_fc2_shape_ok(int dt, int B, int H, int W, int C, int Cin) {
+    return dt == SEGF_BF16 && B > 0 && H > 0 && W > 0 && (Cin == 32 || Cin == 64) && C > 0 && C % 64 == 0 &&
+           (int64_t)B * H * W < (1ll << 31);
+}
+extern "C" int segf_dwconv3x3_gelu_bwd_fc2_supported(int dt, int B, int H, int W, int C_hidden, int C_in) {
+    if (!dw_fc2_shape_ok(dt, B, H, W, C_hidden, C_in)) return 0;
+    if (!dw_use_walk() || dw_small_nch(dt, B, H, W, C_hidden)) return 0;        // the three-pass walk form must be the one in use
+    const int pol = POL(ffn_bwd_fused);
+    if (pol <= 0) return 0;
+    if (pol >= 2) return 1;
+    return (int64_t)B * H * W >= DW_FC2_MIN_ROWS;
+}
+extern "C" int segf_dwconv3x3_gelu_bwd_fc2(int dt, int B, int H, int W, int C_hidden, int C_in, const void* f, const float* w9,
+                                           const float* bias, const void* dys, int64_t ld_dys, const void* w2, void* du, void* dx,
+                                           float* dw, float* db, float* ws, void* stream) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    const int C = C_hidden;
+    if (dt != SEGF_BF16) return SEGF_ERR_DTYPE;
+    // only where segf_dwconv3x3_gelu_bwd runs its three walk passes: segf_dwconv3x3_bwd_blocks then counts THIS call's partial blocks
+    if (!dw_fc2_shape_ok(dt, B, H, W, C, C_in) || !dw_use_walk() || dw_small_nch(dt, B, H, W, C)) return SEGF_ERR_SHAPE;
+    if (((uintptr_t)f % 16) || ((uintptr_t)dys % 16) || ((uintptr_t)w2 % 16) || ((uintptr_t)du % 16) || ((uintptr_t)dx % 16) ||
+        ld_dys < C_in || ld_dys % 8 != 0)
+        return SEGF_ERR_SHAPE;
+    if (!ws) return SEGF_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    typedef bf16_t T;
+    const DwwPlan q = dww_plan(B, H, W, C);
+    float* sums = ws + (int64_t)q.nblk * 10 * C;
+    {
+        const int nslab = C / 64;
+        const int64_t waves = (int64_t)B * q.nseg * ((W + 15) / 16) * nslab;
+        int64_t blocks = (waves + 3) / 4;
+        if (blocks > 32768) blocks = 32768;
+        blocks = (blocks + nslab - 1) / nslab * nslab;          // whole groups of nslab waves: a wave keeps its channel slab (and its W2 fragments)
+        if (C_in == 32)
+            hipLaunchKernelGGL((dwconv3x3_walk_fc2_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)f, w9, bias, (const T*)dys,
+                               ld_dys, (const T*)w2, (T*)du, B, H, W, C, q.R, q.nseg);
+        else
+            hipLaunchKernelGGL((dwconv3x3_walk_fc2_kernel<2>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)f, w9, bias, (const T*)dys,
+                               ld_dys, (const T*)w2, (T*)du, B, H, W, C, q.R, q.nseg);
+    }
+    hipLaunchKernelGGL((dwconv3x3_wgrad_walk_kernel<T>), dim3(q.nblk, q.slabs), dim3(256), 0, st, (const T*)f, (const T*)du, ws,
+                       B, H, W, C, q.ch, q.rl, q.R, q.nseg);
+    dw_walk_launch<T, 1>(st, (const T*)du, w9, (const float*)nullptr, 0, (const T*)nullptr, (T*)dx, B, H, W, C);
+    SEGF_CHECK_LAUNCH();
+    if (!dw) return 0;          // deferred: the partial sums [blocks][10 C] stay in ws, as segf_dwconv3x3_gelu_bwd leaves them
+    colreduce_finalize_launch(ws, q.nblk, 10 * (int64_t)C, sums, st);
+    SEGF_CHECK_LAUNCH();
+    hipLaunchKernelGGL(dw_scatter_kernel, dim3((C + 255) / 256), dim3(256), 0, st, sums, C, dw, db);
+    SEGF_CHECK_LAUNCH();
+    return 0;
 }
 
 // ---- depthwise 7x7 (ConvNeXt Block.dwconv, models/backbones/convnext.py:29,39; convnextv2.py:88,101) ---------------------

@@ -63,6 +63,7 @@
     X(dw_walk_rows, "SEGFAC_DW_WALK_ROWS", 0, "depthwise 3 x 3 walk: rows per segment (0 = chosen from the map size)")                   \
     X(dw_no_small, "SEGFAC_DW_NO_SMALL", 0, "depthwise 3 x 3 backward of small maps: three passes instead of the one-launch LDS form")   \
     X(dw_small_always, "SEGFAC_DW_SMALL_ALWAYS", 0, "... the one-launch form beyond one round of workgroups as well")                    \
+    X(ffn_bwd_fused, "SEGFAC_FFN_BWD_FUSED", 1, "Mix-FFN backward, fc2's data gradient formed inside pass A of the depthwise backward (segf_dwconv3x3_gelu_bwd_fc2_supported): 0 = never, 1 = from 131072 token rows on, 2 = wherever the shape has the kernel") \
     /* ---- decode-head kernels (fuse_map.hip, head_fused.hip, resize.hip) ---- */                                                       \
     X(no_fuse_map, "SEGFAC_NO_FUSE_MAP", 0, "folded SegFormerHead map: streaming product + VALU upsample-add instead of fuse_map_kernel") \
     X(no_bwd248_mfma, "SEGFAC_NO_BWD248_MFMA", 0, "transposed 1/2-1/4-1/8 resizes on the VALU kernel instead of fuse_map_bwd_kernel")    \

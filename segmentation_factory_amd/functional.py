@@ -949,6 +949,75 @@ def dwconv3x3_gelu(x, weight, bias, B, H, W, apply_gelu=True):
     return DWConvGeluFn.apply(x, weight, bias, B, H, W, apply_gelu)
 
 
+@direct_grads(1, 2, 3, 4)
+class DWConvGeluLinearFn(Function):
+    """y = residual + rscale[b] * (gelu(depthwise3x3(x) + b9) W2^T + b2): the tail of MiT's Mix-FFN (mit.py:98-99) as ONE formula, so that
+    its backward never writes the hidden-width gradient of fc2's input: hip.dwconv3x3_gelu_bwd_fc2 rebuilds those values from the
+    C-wide output gradient inside the depthwise backward's first pass.  The forward makes the two calls DWConvGeluFn and LinearFn make;
+    every gradient has the bits of that pair.  The choice of this formula is made at forward time (dwconv3x3_gelu_linear_ok) and the entry point
+    checks the walk form again when the backward runs: a dispatch switch (SEGFAC_DW_NO_WALK, ..._DW_NO_SMALL) flipped between the two makes the
+    backward raise (SEGF_ERR_SHAPE) rather than take another path.  Argument order: fc2's parameters at 1, 2 (the slots _queue_dw reads), the depthwise
+    ones at 3, 4."""
+
+    @staticmethod
+    def forward(ctx, x, weight2, bias2, weight, bias, B, H, W, residual, rscale):
+        x = x if x.is_contiguous() else x.contiguous()
+        M, Cc = x.shape
+        N = weight2.shape[0]
+        w9 = weight.detach().reshape(Cc, 9).contiguous()
+        b = bias.detach().contiguous()
+        g = hip.dwconv3x3_gelu_fwd(x, w9, b, B, H, W, Cc, True)
+        w2 = _w(weight2.reshape(N, -1), x.dtype)
+        y = hip.gemm(0, g, w2, M, N, Cc, bias=bias2.detach(), residual=residual, rscale=rscale, rows_per_group=H * W)
+        ctx.save_for_backward(x, w9, b, g, w2, rscale)
+        ctx.meta = (B, H, W, Cc, N, M, weight.shape, weight2.shape, residual is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w9, b, g, w2, rscale = ctx.saved_tensors
+        B, H, W, Cc, N, M, wshape, w2shape, has_res = ctx.meta
+        dy = _rowmajor(dy)
+        dys = dy
+        if rscale is not None:
+            dys = _take_scaled(dy, rscale, H * W)              # written by the LayerNorm backward that produced dy, when there was one
+            if dys is None:
+                dys = hip.scale_rows(dy, rscale, H * W)
+        dw2 = db2 = None
+        if not _queue_dw(ctx, dys, g, N, Cc, M):
+            dw2, db2 = hip.gemm_dw_db(dys, g, N, Cc, M, split_k=_splitk(N, Cc, M), out=gslot(ctx, 1, (N, Cc)), db_out=gslot(ctx, 2))
+            dw2 = dw2.view(w2shape)
+        gw, gb = gslot(ctx, 3), gslot(ctx, 4)
+        dres = dy if (has_res and ctx.needs_input_grad[8]) else None
+        q = _FIN_QUEUE
+        if q is not None and gw is not None and gb is not None and gb.data_ptr() == gw.data_ptr() + 4 * gw.numel() and gw.is_contiguous():
+            slots = ctx._gslots
+            dx, item = hip.dwconv3x3_gelu_bwd_fc2(x, w9, b, dys, w2, B, H, W, Cc, N, dw_out=gw, db_out=gb, defer=True)
+            q.append((item, (slots[3], slots[4])))
+            if len(q) >= FIN_QUEUE_MAX:
+                _flush_finalizes()
+            return dx, dw2, db2, None, None, None, None, None, dres, None
+        dx, dw, db = hip.dwconv3x3_gelu_bwd_fc2(x, w9, b, dys, w2, B, H, W, Cc, N, dw_out=gw, db_out=gb)
+        return dx, dw2, db2, dw.view(wshape), db, None, None, None, dres, None
+
+
+def dwconv3x3_gelu_linear_ok(x, weight2, bias2, weight, bias, B, H, W):
+    """May gelu(dwconv3x3(x)) -> Linear run as DWConvGeluLinearFn?  The library's shape / size / policy rule
+    (segf_dwconv3x3_gelu_bwd_fc2_supported), a training pass, and all four parameters present and trained."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and torch.is_grad_enabled() and x.requires_grad):
+        return False
+    if bias is None or bias2 is None or not all(p.requires_grad for p in (weight2, bias2, weight, bias)):
+        return False
+    return hip.dwconv3x3_gelu_bwd_fc2_supported(x.dtype, B, H, W, x.shape[1], weight2.shape[0])
+
+
+def dwconv3x3_gelu_linear(x, weight2, bias2, weight, bias, B, H, W, residual=None, rscale=None):
+    y = DWConvGeluLinearFn.apply(x, weight2, bias2, weight, bias, B, H, W, residual, rscale)
+    if rscale is not None:
+        y._segf_dp = (rscale, H * W)                            # as functional.linear tags its residual form
+    return y
+
+
 @direct_grads(1, 2)
 class BatchNormActFn(Function):
     """BatchNorm2d (+ReLU/ReLU6) (+Dropout2d channel scale) on NHWC rows.

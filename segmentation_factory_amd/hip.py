@@ -983,6 +983,38 @@ def dwconv3x3_gelu_bwd(x, w9, bias, dy, B, H, W, Cc, apply_gelu=True, dw_out=Non
     return dx, dw, db
 
 
+def dwconv3x3_gelu_bwd_fc2_supported(dtype, B, H, W, Cc, Cin):
+    """Does the Mix-FFN backward of this shape take the form that builds fc2's data gradient inside pass A (host arithmetic only)?"""
+    dt = BF16 if dtype == torch.bfloat16 else F32
+    return bool(lib().segf_dwconv3x3_gelu_bwd_fc2_supported(dt, B, H, W, Cc, Cin))
+
+
+def dwconv3x3_gelu_bwd_fc2(x, w9, bias, dys, w2, B, H, W, Cc, Cin, dw_out=None, db_out=None, defer=False, return_du=False):
+    """Backward of gelu(dwconv3x3(x) + bias) -> fc2 from fc2's OUTPUT gradient dys [B*H*W, Cin] and w2 [Cin, Cc] (bf16): what
+    gemm(1, dys, w2, M, Cc, Cin) followed by dwconv3x3_gelu_bwd returns, bit for bit, without the [M, Cc] gradient map.  dw_out / db_out /
+    defer as in dwconv3x3_gelu_bwd; return_du appends the scratch du (tests)."""
+    _need_cuda(x, dys, w2)
+    assert x.dtype == dys.dtype == w2.dtype == torch.bfloat16 and x.is_contiguous() and w2.is_contiguous()
+    assert dys.shape == (B * H * W, Cin) and dys.stride(1) == 1 and w2.shape == (Cin, Cc)
+    du = torch.empty_like(x)
+    dx = torch.empty_like(x)
+    ws = _f32(lib().segf_dwconv3x3_bwd_ws(B, H, W, Cc), x.device)
+    if defer:
+        assert dw_out.dtype == db_out.dtype == torch.float32 and dw_out.is_contiguous() and dw_out.numel() == 9 * Cc
+        assert db_out.numel() == Cc and db_out.data_ptr() == dw_out.data_ptr() + 36 * Cc
+        blocks = int(lib().segf_dwconv3x3_bwd_blocks(dt_of(x), B, H, W, Cc))
+        _chk(lib().segf_dwconv3x3_gelu_bwd_fc2(BF16, B, H, W, Cc, Cin, _ptr(x), _ptr(w9), _ptr(bias), _ptr(dys), dys.stride(0), _ptr(w2),
+                                               _ptr(du), _ptr(dx), None, None, _ptr(ws), _stream()), 'segf_dwconv3x3_gelu_bwd_fc2')
+        out = (dx, (ws, blocks, 10 * Cc, dw_out, Cc))
+        return out + (du,) if return_du else out
+    dw = dw_out if dw_out is not None else torch.empty((Cc, 9), dtype=torch.float32, device=x.device)
+    db = db_out if db_out is not None else torch.empty(Cc, dtype=torch.float32, device=x.device)
+    assert dw.is_contiguous() and dw.numel() == Cc * 9 and db.is_contiguous() and db.numel() == Cc and dw.dtype == db.dtype == torch.float32
+    _chk(lib().segf_dwconv3x3_gelu_bwd_fc2(BF16, B, H, W, Cc, Cin, _ptr(x), _ptr(w9), _ptr(bias), _ptr(dys), dys.stride(0), _ptr(w2),
+                                           _ptr(du), _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), _stream()), 'segf_dwconv3x3_gelu_bwd_fc2')
+    return (dx, dw, db, du) if return_du else (dx, dw, db)
+
+
 def dwconv7x7_fwd(x, wt49, bias, B, H, W, Cc):
     """x: [B*H*W, C]; wt49: fp32 [49, C] (transposed depthwise weight)."""
     y = torch.empty_like(x)
