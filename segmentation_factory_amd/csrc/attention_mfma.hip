@@ -1045,7 +1045,12 @@ __global__ void __launch_bounds__(AM_THREADS, 2) attn_mfma_bwd_dkv_kernel(const 
 // at the START of the next tile, behind the barrier that tile needs anyway).  D = rowsum(dO o O) is formed by the threads that
 // stage the dO tile.  Five matrix products per (query tile, key tile) instead of the seven of the two-kernel form, Q / dO / lse
 // read once instead of twice, no D round trip through memory; dK / dV partial slabs as before.
-template <int HD, int KW>
+// CLASSIC = false (the default, policy attn32_classic = 0): the score arithmetic of the EX2 form of attn_mfma_bwd_dkv_kernel --
+// P = exp2(S c - lse log2(e)) with c = scale log2(e) formed once and -lse log2(e) formed by the 32 threads that stage it; -D staged
+// negated and used as the C operand of the dP products (one f32x4 per query tile, shared by the four key tiles); dS = P (dP - D)
+// unscaled, the scale applied once to dK at the slab store and once to dQ in finish_dq.  Per score: v_fma, v_exp, v_mul and the two
+// halves of a bf16 pack.  CLASSIC = true keeps the round-2 arithmetic (subtract, multiply, __expf; (dP - D) scale per score).
+template <int HD, int KW, bool CLASSIC = false>
 __global__ void __launch_bounds__(AM_THREADS, 2) attn_mfma_bwd_fused_kernel(const bf16_t* __restrict__ q, int64_t ldq,
                                                                           const bf16_t* __restrict__ k, int64_t ldk,
                                                                           const bf16_t* __restrict__ v, int64_t ldv,
@@ -1058,7 +1063,7 @@ __global__ void __launch_bounds__(AM_THREADS, 2) attn_mfma_bwd_fused_kernel(cons
     constexpr int KS = HD / 32, DT = HD / 16, WK = 16 * KW, DS_LD = 40;      // DS_LD: row stride (elements) of the dS^T slab
     __shared__ __attribute__((aligned(16))) bf16_t Qs2[2][32 * HD];
     __shared__ __attribute__((aligned(16))) bf16_t dOs2[2][32 * HD];
-    __shared__ float Ls2[2][32], Ds2[2][32];
+    __shared__ __attribute__((aligned(16))) float Ls2[2][32], Ds2[2][32];
     __shared__ __attribute__((aligned(16))) bf16_t dSt[4][WK * DS_LD];       // per wave: dS^T [key][query]
     __shared__ __attribute__((aligned(16))) bf16_t Kst[4][WK * HD];          // per wave: its K rows (read once, transposed)
     __shared__ __attribute__((aligned(16))) float dQp[2][4][2 * DT][64 * 4];  // [buffer][wave][tile (dt, qt)][lane][4]
@@ -1112,40 +1117,50 @@ __global__ void __launch_bounds__(AM_THREADS, 2) attn_mfma_bwd_fused_kernel(cons
     const int sid = threadIdx.x & (NCH - 1);
     const int srow = sid / CPR, scol = (sid - srow * CPR) * 8;
     const bool doQ = threadIdx.x < NCH, doO = !doQ;
-    uint4 rq = make_uint4(0, 0, 0, 0), ro = make_uint4(0, 0, 0, 0);
-    float rl = INFINITY, rd = 0.f;
-    auto fetch = [&](int qt0) {
+    uint4 rx = make_uint4(0, 0, 0, 0), roo = make_uint4(0, 0, 0, 0);          // this thread's chunk of Q or of dO; of O (dO threads)
+    float rl = INFINITY;
+    const float cs = scale * 1.44269504088896340736f;
+    // this thread's chunk of the chunk's first tile; every fetch advances the pointers by 32 rows (the 64-bit row * stride products
+    // of three addresses per tile are formed once)
+    const char* p0 = reinterpret_cast<const char*>(doQ ? Qb + (int64_t)(qbeg + srow) * ldq + scol : dOb + (int64_t)(qbeg + srow) * lddo + scol);
+    const char* p1 = reinterpret_cast<const char*>(Ob + (int64_t)(qbeg + srow) * ldo + scol);
+    const int64_t st0 = 64 * (doQ ? ldq : lddo), st1 = 64 * ldo;          // bytes per 32 rows
+    // fetch ISSUES the loads of a tile and nothing else; every use of what they return (D = rowsum(dO o O), -lse log2(e)) is in put,
+    // behind the tile's products.  (With D formed here the kernel waited vmcnt(0) for Q / dO / O right behind their issue, and once
+    // more for lse: two exposed memory latencies per 32-query tile in front of its 40 matrix instructions.)
+    auto fetch = [&](int qt0) {                              // called once per tile, with qt0 = qbeg, qbeg + 32, ...
         const int row = qt0 + srow;
-        rq = make_uint4(0, 0, 0, 0); ro = make_uint4(0, 0, 0, 0);
-        uint4 oo = make_uint4(0, 0, 0, 0);
-        if (doQ && row < qend) rq = *reinterpret_cast<const uint4*>(Qb + (int64_t)row * ldq + scol);
-        if (doO && row < qend) {
-            ro = *reinterpret_cast<const uint4*>(dOb + (int64_t)row * lddo + scol);
-            oo = *reinterpret_cast<const uint4*>(Ob + (int64_t)row * ldo + scol);
+        rx = make_uint4(0, 0, 0, 0); roo = make_uint4(0, 0, 0, 0);
+        if (row < qend) {
+            rx = *reinterpret_cast<const uint4*>(p0);
+            if (doO) roo = *reinterpret_cast<const uint4*>(p1);
         }
-        const bf16x8 a = __builtin_bit_cast(bf16x8, ro), bq = __builtin_bit_cast(bf16x8, oo);
-        float part = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) part += (float)a[j] * (float)bq[j];
-        part += __shfl_xor(part, 1, 64); part += __shfl_xor(part, 2, 64);          // the four chunks of a row sit in adjacent lanes
-        rd = part;
+        p0 += st0; p1 += st1;
         if (threadIdx.x < 32) {
             const int r2 = qt0 + threadIdx.x;
             rl = r2 < qend ? lb[r2] : INFINITY;          // exp(s - inf) = 0: rows beyond the chunk contribute nothing
         }
     };
     auto put = [&](int buf) {
-        if (doQ) *reinterpret_cast<uint4*>(Qs2[buf] + srow * HD + scol) = rq;
+        const bf16x8 a = __builtin_bit_cast(bf16x8, rx), bq = __builtin_bit_cast(bf16x8, roo);          // (Q threads: O chunk = 0)
+        float part = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) part += (float)a[j] * (float)bq[j];
+        part += __shfl_xor(part, 1, 64); part += __shfl_xor(part, 2, 64);          // the four chunks of a row sit in adjacent lanes
+        if (doQ) *reinterpret_cast<uint4*>(Qs2[buf] + srow * HD + scol) = rx;
         else {
-            *reinterpret_cast<uint4*>(dOs2[buf] + srow * HD + scol) = ro;
-            if ((sid & (CPR - 1)) == 0) Ds2[buf][srow] = rd;
+            *reinterpret_cast<uint4*>(dOs2[buf] + srow * HD + scol) = rx;
+            if ((sid & (CPR - 1)) == 0) Ds2[buf][srow] = CLASSIC ? part : -part;          // -D: the initial value of the dP accumulators
         }
-        if (threadIdx.x < 32) Ls2[buf][threadIdx.x] = rl;
+        if (threadIdx.x < 32) Ls2[buf][threadIdx.x] = CLASSIC ? rl : rl * -1.44269504088896340736f;
     };
     // sum of the waves' partial dQ^T tiles of the PREVIOUS query tile (buffer pb), in wave order; wave w finishes tile w = (dt, qt)
     auto finish_dq = [&](int pb, int qprev) {
         f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int w = 0; w < nwav; ++w) acc += *reinterpret_cast<const f32x4*>(&dQp[pb][w][wave][lane * 4]);
+#pragma unroll
+        for (int w = 0; w < 4; ++w)                          // (written out: as a loop to nwav it was unrolled by eight with a remainder loop)
+            if (w < nwav) acc += *reinterpret_cast<const f32x4*>(&dQp[pb][w][wave][lane * 4]);
+        if (!CLASSIC) acc *= scale;
         const int dt = wave >> 1, qt = wave & 1;
         const int row = qprev + 16 * qt + c;
         if (row < qend) {
@@ -1175,12 +1190,11 @@ __global__ void __launch_bounds__(AM_THREADS, 2) attn_mfma_bwd_fused_kernel(cons
                     Qa[s] = ld_frag_lds(Qs + (16 * qt + c) * HD + 32 * s + 8 * g);
                     dOa[s] = ld_frag_lds(dOs + (16 * qt + c) * HD + 32 * s + 8 * g);
                 }
-                float lr[4], dr[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { lr[r] = Ls[16 * qt + 4 * g + r]; dr[r] = Ds[16 * qt + 4 * g + r]; }
+                const f32x4 lr = *reinterpret_cast<const f32x4*>(Ls + 16 * qt + 4 * g);
+                const f32x4 dr = *reinterpret_cast<const f32x4*>(Ds + 16 * qt + 4 * g);
 #pragma unroll
                 for (int kt = 0; kt < KW; ++kt) {
-                    f32x4 S = (f32x4){0.f, 0.f, 0.f, 0.f}, dP = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    f32x4 S = (f32x4){0.f, 0.f, 0.f, 0.f}, dP = CLASSIC ? (f32x4){0.f, 0.f, 0.f, 0.f} : dr;
 #pragma unroll
                     for (int s = 0; s < KS; ++s) {
                         S = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Qa[s], Kf[kt][s], S, 0, 0, 0);
@@ -1188,9 +1202,9 @@ __global__ void __launch_bounds__(AM_THREADS, 2) attn_mfma_bwd_fused_kernel(cons
                     }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const float p = __expf(S[r] * scale - lr[r]);
+                        const float p = CLASSIC ? __expf(S[r] * scale - lr[r]) : __builtin_amdgcn_exp2f(fmaf(S[r], cs, lr[r]));
                         P[qt][kt][r] = p;
-                        dS[qt][kt][r] = p * (dP[r] - dr[r]) * scale;
+                        dS[qt][kt][r] = CLASSIC ? p * (dP[r] - dr[r]) * scale : p * dP[r];
                     }
                     // dS^T slab: key 16 kt + c, queries 16 qt + 4 g .. + 3
                     *reinterpret_cast<uint2*>(dSt[wave] + (16 * kt + c) * DS_LD + 16 * qt + 4 * g) =
@@ -1247,6 +1261,7 @@ __global__ void __launch_bounds__(AM_THREADS, 2) attn_mfma_bwd_fused_kernel(cons
             float* row = sb + ((int64_t)b * Nkv + key) * 2 * C + h * HD;
 #pragma unroll
             for (int d = 0; d < DT; ++d) {
+                if (!CLASSIC) dK[d][kt] *= scale;
                 *reinterpret_cast<float4*>(row + 16 * d + 4 * g) = make_float4(dK[d][kt][0], dK[d][kt][1], dK[d][kt][2], dK[d][kt][3]);
                 *reinterpret_cast<float4*>(row + C + 16 * d + 4 * g) = make_float4(dV[d][kt][0], dV[d][kt][1], dV[d][kt][2], dV[d][kt][3]);
             }
@@ -1264,13 +1279,22 @@ int attn_mfma_bwd(int hd, int B, int heads, int N, int Nkv, const void* q, int64
     const bf16_t* O = (const bf16_t*)o; const bf16_t* DO = (const bf16_t*)d_o;
     if (hd == 32 && Nkv <= 256 && !POL(attn_no_fused_bwd)) {      // one workgroup owns all keys: dQ, dK, dV in one kernel
         dim3 g3(1, nchunk, B * heads);
-        hipLaunchKernelGGL((attn_mfma_bwd_fused_kernel<32, 4>), g3, dim3(AM_THREADS), 0, st, Q, ldq, K, ldk, V, ldv, O, ldo, DO, lddo, lse,
-                           (bf16_t*)dq, lddq, slab, heads, N, Nkv, B, qchunk, scale);
+        if (POL(attn32_classic))
+            hipLaunchKernelGGL((attn_mfma_bwd_fused_kernel<32, 4, true>), g3, dim3(AM_THREADS), 0, st, Q, ldq, K, ldk, V, ldv, O, ldo, DO, lddo, lse,
+                               (bf16_t*)dq, lddq, slab, heads, N, Nkv, B, qchunk, scale);
+        else
+            hipLaunchKernelGGL((attn_mfma_bwd_fused_kernel<32, 4>), g3, dim3(AM_THREADS), 0, st, Q, ldq, K, ldk, V, ldv, O, ldo, DO, lddo, lse,
+                               (bf16_t*)dq, lddq, slab, heads, N, Nkv, B, qchunk, scale);
     } else if (hd == 32) {
         hipLaunchKernelGGL((attn_mfma_bwd_dq_kernel<32, QW, false, 4, false>), g1, dim3(AM_THREADS), 0, st, Q, ldq, K, ldk, V, ldv, O, ldo, DO, lddo,
                            lse, (bf16_t*)dq, lddq, Dbuf, heads, N, Nkv, scale);
-        hipLaunchKernelGGL((attn_mfma_bwd_dkv_kernel<32, false, false>), g2, dim3(AM_THREADS), 0, st, Q, ldq, K, ldk, V, ldv, DO, lddo, lse, Dbuf,
-                           slab, heads, N, Nkv, B, qchunk, scale);
+        // the key side takes the fused kernel's arithmetic in the same order (dK / dV of the two forms are bitwise equal): EX2 unless classic
+        if (POL(attn32_classic))
+            hipLaunchKernelGGL((attn_mfma_bwd_dkv_kernel<32, false, false>), g2, dim3(AM_THREADS), 0, st, Q, ldq, K, ldk, V, ldv, DO, lddo, lse, Dbuf,
+                               slab, heads, N, Nkv, B, qchunk, scale);
+        else
+            hipLaunchKernelGGL((attn_mfma_bwd_dkv_kernel<32, false, false, true>), g2, dim3(AM_THREADS), 0, st, Q, ldq, K, ldk, V, ldv, DO, lddo, lse,
+                               Dbuf, slab, heads, N, Nkv, B, qchunk, scale);
     } else {
 #define AM_DQ(P2, OCCv, SWv) hipLaunchKernelGGL((attn_mfma_bwd_dq_kernel<64, QW, P2, OCCv, SWv>), g1, dim3(AM_THREADS), 0, st, Q, ldq, K, ldk, V, ldv, O, ldo, \
         DO, lddo, lse, (bf16_t*)dq, lddq, Dbuf, heads, N, Nkv, scale)

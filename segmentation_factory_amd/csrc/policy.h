@@ -58,6 +58,7 @@
     X(attn64_prescale, "SEGFAC_ATTN64_PRESCALE", 0, "head dim 64, >= 128 keys: scale log2(e) rides on the Q fragments (bf16(q c), one more rounding per q element) and -max / -lse are the score accumulators' initial values, instead of one multiply-add per score: forward + query-side backward, +8 % / +2 % per kernel, attention error x 1.2 - 2.3") \
     X(attn64_dkv_rows, "SEGFAC_ATTN64_DKV_ROWS", 128, "head dim 64, >= 128 keys, key-side backward: query rows per staged Q / dO tile and barrier (128, 64 or 32: the same arithmetic, bit for bit)") \
     X(attn_no_fused_bwd, "SEGFAC_ATTN_NO_FUSED_BWD", 0, "head dim 32, <= 256 keys: query-side + key-side backward kernels instead of the one-kernel backward") \
+    X(attn32_classic, "SEGFAC_ATTN32_CLASSIC", 0, "head dim 32 backward (one-kernel and key-side kernels): the round-2 score arithmetic (subtract, multiply, __expf; (dP - D) scale per score) instead of P = exp2(S c - lse log2(e)) with -D as the C operand of the dP products and the scale applied once to dK and dQ") \
     /* ---- depthwise / patch convolutions (conv.hip) ---- */                                                                            \
     X(dw_no_walk, "SEGFAC_DW_NO_WALK", 0, "depthwise 3 x 3: the round-1 strip kernels instead of the vertical-walk kernels")             \
     X(dw_walk_rows, "SEGFAC_DW_WALK_ROWS", 0, "depthwise 3 x 3 walk: rows per segment (0 = chosen from the map size)")                   \
