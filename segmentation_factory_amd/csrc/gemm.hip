@@ -18,31 +18,32 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 
+// The kernel argument block of the GEMM family.  Every member has a default: a launcher sets what differs.
 struct GemmArgs {
-    const void* A; const void* B; void* C;
-    const float* bias; const void* residual; const float* rscale;
-    int64_t M, N, K, lda, ldb, ldc, ldr, rpg;
-    int64_t kchunk;          // K range per grid.z slice
-    float* ws;               // split-K partials [z][M][N] (nullptr when split_k == 1)
-    int a_vec, b_vec, c_vec, r_vec, use_tr;
-    int fast;                // uniform guard-free tile loads for full K steps (debug switch SEGFAC_GEMM_NO_FASTLOAD)
-    int xcd_slabs;           // layout 2, split-K: the tiles of one K slab on one XCD (gemm_bf16_tile)
-    int c_vec16;             // C rows allow 16-byte stores (bf16 output, LDS-staged epilogue)
+    const void* A = nullptr; const void* B = nullptr; void* C = nullptr;
+    const float* bias = nullptr; const void* residual = nullptr; const float* rscale = nullptr;
+    int64_t M = 0, N = 0, K = 0, lda = 0, ldb = 0, ldc = 0, ldr = 0, rpg = 1;
+    int64_t kchunk = 0;        // K range per grid.z slice
+    float* ws = nullptr;        // split-K partials [z][M][N] (nullptr when split_k == 1)
+    int a_vec = 0, b_vec = 0, c_vec = 0, r_vec = 0, use_tr = 0;
+    int fast = 0;        // uniform guard-free tile loads for full K steps (debug switch SEGFAC_GEMM_NO_FASTLOAD)
+    int xcd_slabs = 0;        // layout 2, split-K: the tiles of one K slab on one XCD (gemm_bf16_tile)
+    int c_vec16 = 0;        // C rows allow 16-byte stores (bf16 output, LDS-staged epilogue)
     // implicit 3x3 convolution (stride 1, pad 1) over an NHWC operand [B][cH][cW][ld >= cC]: the gathered operand's K (layout 0,
     // operand A) or N (layout 2, operand B) axis is (tap = ky*3+kx, channel); csign = +1 reads pixel + offset(tap) (forward,
     // weight gradient), -1 reads pixel - offset(tap) (data gradient = correlation of dy with the transposed weights)
-    int cH, cW, cC, csign;
+    int cH = 0, cW = 0, cC = 0, csign = 1;
     // layout 2 only: colsum[m] = sum_k A(k, m) (the bias gradient next to the weight gradient): the first unused column of the
     // last column tile is staged as all-ones, so its accumulators are the column sums; colsum_ws = split-K partials [z][M]
-    float* colsum; float* colsum_ws;
+    float* colsum = nullptr; float* colsum_ws = nullptr;
     // operand prologue (256-tile kernel, layouts 0 / 2): the ACTIVATION operand (A in layout 0, B in layout 2) is read as
     // act(x * pro_scale[g][f] + pro_shift[g][f]), g = token / pro_rpg, f = feature -- BatchNorm(+ReLU)(+Dropout2d scale) of
     // the producer applied on the way into LDS, so the normalised tensor is never materialised
-    const float* pro_scale; const float* pro_shift; int64_t pro_rpg; int64_t pro_ld; int pro_act;
+    const float* pro_scale = nullptr; const float* pro_shift = nullptr; int64_t pro_rpg = 1; int64_t pro_ld = 0; int pro_act = 0;
     // fp8 operands (256-tile kernel, layout 0, template FP8): A / B hold OCP fp8 bytes and every K-axis quantity of this struct (K,
     // lda, ldb, kchunk, cC) counts 2-BYTE UNITS -- the loaders and LDS images move bytes and never look inside -- C[m][n] =
     // acc * f8_sa[0] * f8_sb[n]: one dequantisation scale for the activation tensor, one per weight row
-    const float* f8_sa; const float* f8_sb;
+    const float* f8_sa = nullptr; const float* f8_sb = nullptr;
 };
 
 #define GB_BM 128
@@ -1138,8 +1139,9 @@ __global__ void __launch_bounds__(GG_THREADS) gemm_bf16_big_kernel(GemmArgs a) {
     }
 }
 
-// one decision for both the launcher and the split-K / workspace sizing: the 256^2 tile when both dimensions exceed one
-// 128 tile, K spans more than one step, and the launch still has enough workgroups for 256 CUs
+// The 256^2 tile by SHAPE: both dimensions exceed one 128 tile, K spans more than one step, and the launch still has enough
+// workgroups for 256 CUs.  Asked only by gemm_tile_shape (host dispatch, below): the launchers, the slice-count and workspace
+// queries and the *_supported answers all read the shape rule there.
 static inline bool gemm_use_big(int layout, int64_t M, int64_t N, int64_t K) {
     if (POL(gemm_no_big)) return false;
     if (M <= 128 || N <= 128 || K <= GB_BK) return false;
@@ -1510,9 +1512,8 @@ static inline unsigned splitk_reduce_cs_blocks(int form, int64_t cs_n) { return 
 // segf_gemm_dw_db_grouped collects the reduce passes of the products it cannot group (streaming / 256-tile kernels) here and issues
 // them as grouped launches too: while the sink is set, gemm_impl appends its fp32 reduce instead of launching it
 static thread_local ReduceGroup* g_reduce_sink = nullptr;
-static bool reduce_sink_take(const float* ws, int split, int64_t M, int64_t N, float* C, int64_t ldc, const float* cs_ws, float* cs_out,
-                             int64_t cs_n) {
-    ReduceGroup* r = g_reduce_sink;
+static bool reduce_group_add(ReduceGroup* r, const float* ws, int split, int64_t M, int64_t N, float* C, int64_t ldc, const float* cs_ws,
+                             float* cs_out, int64_t cs_n) {
     if (!r || r->n >= GDW_MAX) return false;
     const int k = r->n;
     const int form = splitk_reduce_form(ws, M, N, C, ldc);
@@ -1960,13 +1961,13 @@ static int gemm_skinny_nt(int layout, int64_t M, int64_t N, int64_t K) {
     while (nt >= 2 && N % (16 * nt)) nt >>= 1;
     return nt >= 2 ? nt : 0;
 }
+#define SK(KS_, NT_) if (ks == KS_ && nt == NT_) { hipLaunchKernelGGL((gemm_skinny_kernel<LAYOUT, KS_, NT_>), grid, dim3(256), 0, st, a); return true; }
 template <int LAYOUT>
 static bool gemm_skinny_launch(int ks, int nt, dim3 grid, hipStream_t st, const GemmArgs& a) {
-#define SK(KS_, NT_) if (ks == KS_ && nt == NT_) { hipLaunchKernelGGL((gemm_skinny_kernel<LAYOUT, KS_, NT_>), grid, dim3(256), 0, st, a); return true; }
     SK(1, 2) SK(1, 4) SK(1, 8) SK(2, 2) SK(2, 4) SK(2, 8) SK(4, 2) SK(4, 4) SK(5, 2)
-#undef SK
     return false;
 }
+#undef SK
 
 // ---- streaming weight gradient for small outputs -----------------------------------------------------------------------------
 // dW[M,N] = A^T B over K ~ 10^5..10^6 tokens with M, N <= a few hundred (the MiT stage-1/2 linears, the patch embedding) is
@@ -2129,17 +2130,19 @@ static bool gemm_dw_skinny_plan(int64_t M, int64_t N, int64_t K, bool colsum, Dw
     p.slices = (int)cdiv64(K, kchunk);
     return true;
 }
-template <int MT>
-static bool gemm_dw_skinny_launch_nt(int nt, dim3 grid, hipStream_t st, const GemmArgs& a, int slices) {
 #define DS(NT_) if (nt == NT_) { if (a.colsum_ws) hipLaunchKernelGGL((gemm_dw_skinny_kernel<MT, NT_, true>), grid, dim3(256), 0, st, a, slices); \
                             else hipLaunchKernelGGL((gemm_dw_skinny_kernel<MT, NT_, false>), grid, dim3(256), 0, st, a, slices); return true; }
+template <int MT>
+static bool gemm_dw_skinny_launch_nt(int nt, dim3 grid, hipStream_t st, const GemmArgs& a, int slices) {
     DS(2)
     if constexpr (MT <= 4) { DS(4) DS(8) }
     if constexpr (MT == 2) { DS(10) }
-#undef DS
     return false;
 }
+#undef DS
 
+// ---- host dispatch: one route decision (gemm_plan) and one argument builder (gemm_args) for every linear product; the slice-count /
+// *_supported queries and the 3 x 3 convolutions read the shape part of the decision (gemm_tile_shape) and add their own rules ----
 // nn.Linear weight gradients that are MATRIX-PIPE work, not streaming: dW [M x N] = dy^T x over K tokens with both feature counts
 // multiples of 256, >= 100 GFLOP and >= 256 FLOP per operand byte (ConvNeXtV2-L stage 3 / 4 at 640^2, batch 32: [3072 x 768] over
 // 51200 tokens = 241 GFLOP, 27 blocks x 2; MiT-B2 stage 4 at batch 32).  gemm_use_big's token-count rule (K >= 65536, made for the
@@ -2152,13 +2155,22 @@ static inline bool dw_on_gemm8(int64_t M, int64_t N, int64_t K) {
     const double gflop = 2e-9 * (double)M * (double)N * (double)K;
     return gflop >= (double)POL(gemm8_dw_min_gflop) && M * N >= 256 * (M + N);
 }
+// The tile a product's SHAPE asks for, before alignment, epilogue and kernel-support checks: what the launcher starts from and all
+// that the slice-count and workspace queries know.  Eight = the eight-phase tile for a weight gradient below the token-count bar.
+// no_big: the answer as if the 256-tile kernel did not exist (segf_gemm_dw_db_grouped's one exception).
+enum class TileShape { Tile128, Big, Eight };
+static TileShape gemm_tile_shape(int layout, int64_t M, int64_t N, int64_t K, bool no_big = false) {
+    if (!no_big && gemm_use_big(layout, M, N, K)) return TileShape::Big;
+    return layout == 2 && dw_on_gemm8(M, N, K) ? TileShape::Eight : TileShape::Tile128;
+}
 extern "C" int segf_gemm_pick_splitk(int64_t M, int64_t N, int64_t K) {
     // layout 2 (weight gradient): K = token count.  Aim for >= 512 workgroups, >= 4 K-steps per slice.
     {   // small outputs: the streaming kernel's slice count (one slice per wave); the bias-gradient column is assumed
         DwSkinny p;
         if (gemm_dw_skinny_plan(M, N, K, true, p)) return p.slices;
     }
-    if (!gemm_use_big(2, M, N, K) && dw_on_gemm8(M, N, K)) {
+    const TileShape shape = gemm_tile_shape(2, M, N, K);
+    if (shape == TileShape::Eight) {
         // one 256 x 256 tile per CU and round: the smallest slice count (slices of >= 16 K tiles) whose last round is >= 90 % full, else
         // the fullest ([6144 x 1536] = 144 tiles: 5 slices = 720 workgroups = 2.8 rounds; [3072 x 768] = 36 tiles: 7 slices = 252)
         const int64_t tiles = (M / 256) * (N / 256);
@@ -2172,7 +2184,7 @@ extern "C" int segf_gemm_pick_splitk(int64_t M, int64_t N, int64_t K) {
         }
         return best;
     }
-    const bool big = gemm_use_big(2, M, N, K);
+    const bool big = shape == TileShape::Big;
     const int64_t tiles = big ? cdiv64(M, GG_B) * cdiv64(N, GG_B) : cdiv64(M, GB_BM) * cdiv64(N, GB_BN);
     // one wave of workgroups: 256 CUs x (1 big-tile | 2 small-tile) resident workgroups.  Rounded DOWN: 3 tiles x 86 slices =
     // 258 workgroups would run as two rounds (256 + 2) and take twice as long as 3 x 85
@@ -2195,7 +2207,6 @@ extern "C" int segf_gemm_pick_splitk(int64_t M, int64_t N, int64_t K) {
     return (int)s;
 }
 
-struct GemmPro { const float* scale; const float* shift; int64_t rpg; int64_t ld; int act; };
 // gemm8.hip: the eight-phase 256 x 256 tile (LDS-DMA staging, counted waits).  kind 0 / 1 / 2 = layout 0 / 1 / 2; conv = implicit 3x3
 int gemm8_supported(int kind, int conv, int64_t M, int64_t N, int64_t K, int64_t kchunk, int cC);
 int gemm8_linear_ok(int64_t M, int64_t N, int64_t K, int64_t kchunk);
@@ -2203,10 +2214,334 @@ int gemm8_launch(int kind, int conv, int fp8, int64_t M, int64_t N, int64_t K, i
                  const void* B, int64_t ldb, void* C, int64_t ldc, int cH, int cW, int cC, int csign, const float* f8_sa,
                  const float* f8_sb, const float* bias, const void* residual, int64_t ldr, const float* rscale, int64_t rpg, float* ws,
                  hipStream_t st);
+// The eight-phase tile (gemm8.hip) for nn.Linear products (layouts 0 / 1) with plain epilogues: the shape part of the rule.  r03 measured
+// it as a loss on every BASELINE model (12-load prologue, drain, direct 8-byte stores against 4 .. 48 K tiles); after the read-section
+// diet of r05 it wins wherever it has >= 192 tiles to run, from K = 256 on, ragged last tiles included (tools/probe/linear8_probe.py,
+// same process, us: [12800 x 3072] K = 768 102 -> 84; [12800 x 768] K = 3072 (150 tiles) 98 -> 69; [51200 x 384] K = 1536 (75 % of the
+// launched tiles are output) 108 -> 77; [131072 x 320] K = 1280 (62.5 %) 219 -> 152; [131072 x 1280] K = 320 220 -> 197; [3200 x 6144]
+// K = 1536 106 -> 80; [32768 x 512] K = 2048 74 -> 57 = 1.21 PFLOP/s).  Not taken: fewer than 128 tiles (78 .. 96 tiles: -2 .. +6 %), and
+// 128 .. 191 tiles unless K >= 2048.  SEGFAC_GEMM8_LINEAR=0 switches it off (cfg5 101.8 -> 98.9 images/s, same box).
+static bool gemm8_linear_fits(int64_t M, int64_t N, int64_t K) {
+    // whole-tile count the launch pays for, and the share of it that is output (ragged last tiles: [51200 x 384] = 75 %)
+    const int64_t tiles8 = cdiv64(M, 256) * cdiv64(N, 256);
+    const bool dense = 100 * M * N >= (int64_t)POL(gemm8_linear_min_fill) * tiles8 * 65536;
+    // ... and only where the gain pays for what a launch of this kernel costs the kernels AFTER it (in-situ traces of the cfg2 / cfg4
+    // step, tools/probe/trace_ab.sh: the launches that followed an eight-phase launch ran 3 - 10 % longer -- the chip gives clock back
+    // after the dense MFMA burst -- ~10 us per launch summed over the step): the gain is ~20 - 30 % of the product's time, i.e. worth it
+    // from ~36 GFLOP on (K >= 512) and, for the 4 - 7 K tiles of a shorter reduction, from ~100 GFLOP on.
+    const double gflop = 2e-9 * (double)M * (double)N * (double)K;
+    const bool worth = gflop >= (K >= 512 ? (double)POL(gemm8_linear_min_gflop) : 100.0);
+    return K >= POL(gemm8_linear_min_k) && dense && worth && (tiles8 >= 192 || (tiles8 >= POL(gemm8_linear_min_tiles) && K >= 2048));
+}
+
+struct GemmPro { const float* scale; const float* shift; int64_t rpg; int64_t ld; int act; };
+// K range of one slice for a request of split_k slices (whole K steps of the data type's kernels)
+static inline int64_t gemm_kchunk(int dt, int64_t K, int split_k) {
+    const int64_t kstep = dt == SEGF_BF16 ? GB_BK : GF_BK;
+    const int64_t kchunk = cdiv64(cdiv64(K, split_k < 1 ? 1 : split_k), kstep) * kstep;
+    return kchunk > 0 ? kchunk : kstep;
+}
+static inline int gemm_slices(int64_t K, int64_t kchunk) { return (int)cdiv64(K > 0 ? K : 1, kchunk); }
+// The kernel arguments of a plain linear product: slices of kchunk along K (partials in ws when there are several), colsum = where the
+// bias gradient goes if it rides on a weight gradient (its partials behind the product's in ws).
+static GemmArgs gemm_args(int dt, int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb,
+                          void* C, int c_dt, int64_t ldc, const float* bias, const void* residual, int64_t ldr, const float* rscale,
+                          int64_t rows_per_group, int64_t kchunk, float* ws, float* colsum, const GemmPro* pro) {
+    GemmArgs a;
+    a.A = A; a.B = B; a.C = C; a.bias = bias; a.residual = residual; a.rscale = rscale;
+    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldr = ldr; a.rpg = rows_per_group > 0 ? rows_per_group : 1;
+    const int slices = gemm_slices(K, kchunk);
+    a.kchunk = kchunk;
+    a.ws = slices > 1 ? ws : nullptr;
+    const size_t esz = dt == SEGF_BF16 ? 2 : 4, csz = c_dt == SEGF_BF16 ? 2 : 4;
+    a.a_vec = ((uintptr_t)A % 16 == 0) && ((lda * esz) % 16 == 0);
+    a.b_vec = ((uintptr_t)B % 16 == 0) && ((ldb * esz) % 16 == 0);
+    a.fast = POL(gemm_no_fastload) ? 0 : 1;
+    a.xcd_slabs = (layout == 2 && slices > 1 && !POL(dw_no_xcd_slabs)) ? 1 : 0;
+    // bit 0: vector loads allowed, bit 1: guard-free full-K-step loads.  Layouts 0 / 1 gain 25-45 % from the latter; the split-K
+    // weight-gradient launches (layout 2) measured 8-15 % SLOWER with every load in flight, so they keep the guarded loads
+    if (a.fast && layout != 2) { a.a_vec *= 3; a.b_vec *= 3; }
+    a.c_vec = ((uintptr_t)C % (4 * csz) == 0) && ((ldc * csz) % (4 * csz) == 0);
+    a.r_vec = residual ? (((uintptr_t)residual % 16 == 0) && ((ldr * esz) % 16 == 0)) : 0;
+    a.c_vec16 = ((uintptr_t)C % 16 == 0) && ((ldc * csz) % 16 == 0);
+    a.colsum = colsum;
+    a.colsum_ws = (colsum && slices > 1) ? ws + (int64_t)slices * M * N : nullptr;
+    if (pro) { a.pro_scale = pro->scale; a.pro_shift = pro->shift; a.pro_rpg = pro->rpg; a.pro_ld = pro->ld; a.pro_act = pro->act; }
+    a.use_tr = POL(gemm_no_tr) ? 0 : 1;      // debugging switch: transposed fragments by scalar LDS loads instead of ds_read_b64_tr_b16
+    return a;
+}
+
+// The route of a linear product: which kernel family and form, over which grid.  gemm_plan launches nothing and allocates nothing.
+enum class GemmFamily { None, SkinnyRows, SkinnyK, Skinny, DwSkinny, Eight, Big, Tile128, F32Mfma, F32Fma };
+struct GemmPlan {
+    GemmFamily family = GemmFamily::None;
+    int err = 0;                          // family None: what the call returns
+    TileShape shape = TileShape::Tile128;
+    int slices = 1; int64_t kchunk = 0;   // effective slice count, kchunk tokens each
+    dim3 grid;
+    bool colsum_rides = false;            // the bias gradient is formed by the product's kernel (else: a column-sum pass of its own)
+    bool reduce = false;                  // a split-K reduce pass follows
+    bool f32_out = false;                 // the kernel writes fp32 (C itself or the split-K partials)
+    bool deep = false, one_step = false;  // 256-tile (layout 0) / 128-tile: two K steps of loads in flight; 128-tile: the single-K-step form
+    bool narrow = false, wide = false;    // 256-tile: the narrow wave shape of its layout; fp32 MFMA: one 128 x (32 nt) column tile / 128 x 128 tiles
+    int ks = 0, nt = 0;                   // streaming kernels: K steps / column tiles per wave
+    DwSkinny sk{};                        // streaming weight gradient: its blocking
+};
+static GemmPlan gemm_plan_none(GemmPlan p, int err) { p.family = GemmFamily::None; p.err = err; return p; }
+// dt / c_dt / layout, the arguments gemm_args built (sizes, alignment bits, which of bias / residual / colsum / prologue / ws are
+// present) and the slice count the caller asked for (and sized ws with).  skip: plan as if these kernels did not exist.
+enum { PLAN_NO_BIG = 1, PLAN_NO_EIGHT = 2, PLAN_NO_DW_SKINNY = 4 };
+static GemmPlan gemm_plan(int dt, int c_dt, int layout, const GemmArgs& a, int split_k, unsigned skip = 0) {
+    const int64_t M = a.M, N = a.N, K = a.K;
+    GemmPlan p;
+    p.kchunk = a.kchunk;
+    p.slices = gemm_slices(K, a.kchunk);
+    p.reduce = a.ws != nullptr;
+    p.f32_out = c_dt == SEGF_F32 || a.ws;
+    if (dt != SEGF_BF16) {
+        p.grid = dim3((unsigned)cdiv64(N, GF_BN), (unsigned)cdiv64(M, GF_BM), (unsigned)p.slices);
+        if (p.grid.y > 65535u) return gemm_plan_none(p, SEGF_ERR_SHAPE);
+        p.family = GemmFamily::F32Fma;
+        if (!POL(gemm_f32_no_mfma)) {               // exact fp32 on the matrix pipe
+            // 128 x 128 tiles when they still give every CU a workgroup (or the output is so large that operand traffic decides); a
+            // narrow output (N <= 160) over many rows in ONE column tile of 128 x (32 TN); 64 x 64 otherwise
+            const int64_t big_tiles = cdiv64(M, 128) * cdiv64(N, 128) * p.slices;
+            p.narrow = N <= 160 && cdiv64(M, 128) * p.slices >= 192;
+            p.nt = (int)cdiv64(N, 32);
+            p.wide = !p.narrow && M >= 128 && N >= 96 && big_tiles >= 192;
+            p.grid = dim3((unsigned)(p.narrow ? 1 : cdiv64(N, p.wide ? 128 : 64)), (unsigned)cdiv64(M, (p.wide || p.narrow) ? 128 : 64), (unsigned)p.slices);
+            if (p.grid.y > 65535u) return gemm_plan_none(p, SEGF_ERR_SHAPE);
+            p.family = GemmFamily::F32Mfma;
+        }
+        return p;
+    }
+    const bool pro = a.pro_scale != nullptr, vec = (a.a_vec & 1) && (a.b_vec & 1);
+    p.shape = gemm_tile_shape(layout, M, N, K, skip & PLAN_NO_BIG);
+    // streaming products: bf16 in and out, no slices, vectorisable rows
+    if (!pro && c_dt == SEGF_BF16 && p.slices == 1 && a.a_vec && a.c_vec16 && (!a.residual || a.r_vec) && (layout == 1 || a.b_vec) &&
+        !POL(gemm_no_skinny)) {
+        const int64_t groups = cdiv64(M, 16);
+        if (layout == 0 && !a.residual && K == 32 && N == 768 && M >= 65536 && a.b_vec && !POL(gemm_no_skinny_rows)) {
+            p.family = GemmFamily::SkinnyRows;
+            p.grid = dim3((unsigned)imin64(cdiv64(groups, 4 * 8), 1024));
+            return p;
+        }
+        if (gemm_skinny_k_ok(layout, M, N, K) && a.ldc % 4 == 0 && (!a.residual || a.ldr % 2 == 0)) {
+            p.family = GemmFamily::SkinnyK;
+            p.grid = dim3((unsigned)imin64(groups, 256 * 12));     // several rounds of 16-token groups per workgroup
+            p.ks = (int)(K / 128);
+            return p;
+        }
+        p.nt = gemm_skinny_nt(layout, M, N, K);
+        if (p.nt) {
+            p.family = GemmFamily::Skinny;
+            p.grid = dim3((unsigned)imin64(cdiv64(groups, 4 * 4), 2048), (unsigned)(N / (16 * p.nt)));      // >= 4 token groups per wave
+            p.ks = (int)(K / 32);
+            return p;
+        }
+    }
+    // the caller sized ws for its slice count (segf_gemm_pick_splitk gives the streaming kernel's): the streaming weight gradient only then
+    const bool streaming = !(skip & PLAN_NO_DW_SKINNY) && layout == 2 && !pro && a.ws && c_dt == SEGF_F32 && a.use_tr && vec && !a.bias && !a.residual &&
+                           gemm_dw_skinny_plan(M, N, K, true, p.sk) && p.sk.slices == p.slices && a.kchunk % 32 == 0 &&
+                           a.lda * 2 * 32 < (1ll << 31) && a.ldb * 2 * 32 < (1ll << 31);
+    // the bias gradient rides in the streaming kernel (all-ones fragment) and in the 128-tile kernel (all-ones column when N leaves one
+    // free, extra MFMAs when it does not); the 256-tile and eight-phase kernels have no registers to spare for it.  (In the streaming
+    // kernel only when the REQUESTED count is its own, not merely the effective one: kept as found, the sweep golden pins it.)
+    p.colsum_rides = a.colsum && layout == 2 && c_dt == SEGF_F32 && !POL(gemm_no_fused_db) &&
+                     ((streaming && p.sk.slices == split_k) || p.shape == TileShape::Tile128);
+    if (streaming) {
+        p.family = GemmFamily::DwSkinny;
+        p.grid = dim3((unsigned)((p.sk.slices + 3) / 4), (unsigned)p.sk.colblocks, (unsigned)p.sk.rowblocks);
+        return p;
+    }
+    // the eight-phase tile: plain epilogues, no bias-gradient column
+    if (!(skip & PLAN_NO_EIGHT) && !pro && a.use_tr && !p.colsum_rides && vec && POL(gemm8_linear) && M > 128 && N > 128) {
+        const bool eight = layout != 2 ? gemm8_linear_fits(M, N, K) && !p.f32_out && p.slices == 1 && gemm8_linear_ok(M, N, K, a.kchunk) &&
+                                             (!a.residual || a.r_vec)
+                                       : p.shape != TileShape::Tile128 && c_dt == SEGF_F32 && !a.bias && !a.residual &&
+                                             gemm8_supported(2, 0, M, N, K, a.kchunk, 0);
+        if (eight) { p.family = GemmFamily::Eight; return p; }
+    }
+    // short reductions (K <= 704: the MiT stage-3 / 4 linears at 160 / 640 / 256) stay on the 128-tile kernel: with a handful of K
+    // steps the 256-tile kernel's operand reuse buys nothing (the product is bound by its output) and its one workgroup per CU
+    // exposes every load -> LDS -> MFMA round trip; two workgroups per CU with two K steps in flight: cfg2 +0.4 %, batch 16
+    // +0.7 %, cfg4 +0.2 % (same box).  The narrow shapes (N <= 160) keep their one-tile kernel; the implicit-GEMM convolutions
+    // (other entry points) are not concerned.
+    const bool short_k = layout != 2 && K <= 704 && N > 160 && !pro;
+    if (((p.shape == TileShape::Big && !short_k) || pro) && a.use_tr) {
+        p.grid = dim3((unsigned)cdiv64(N, GG_B), (unsigned)cdiv64(M, GG_B), (unsigned)p.slices);
+        if (p.grid.y > 65535u) return gemm_plan_none(p, SEGF_ERR_SHAPE);
+        p.family = GemmFamily::Big;
+        // partly filled workgroup tiles: the narrow wave shapes (see the kernel's header)
+        p.narrow = !POL(gemm_no_narrow) && (layout == 0 ? !p.f32_out && N <= 160 : layout == 1 ? !p.f32_out && !pro && N <= 160 : p.f32_out && M <= 160);
+        p.deep = layout == 0 && p.slices == 1 && (a.a_vec & 2) && (a.b_vec & 2) && K % GB_BK == 0 && K >= 2 * GB_BK &&
+                 (!pro || a.pro_ld <= 1024) && !POL(gemm_no_deep);
+        return p;
+    }
+    if (pro) return gemm_plan_none(p, SEGF_ERR_SHAPE);            // only the 256-tile kernel applies operand prologues
+    p.grid = dim3((unsigned)cdiv64(N, GB_BN), (unsigned)cdiv64(M, GB_BM), (unsigned)p.slices);
+    if (p.grid.y > 65535u) return gemm_plan_none(p, SEGF_ERR_SHAPE);
+    p.family = GemmFamily::Tile128;
+    p.one_step = a.kchunk <= GB_BK && layout != 2;     // single K step: the 34 KB single-buffer variant
+    // two K steps in flight (branch-free loaders) whenever the operands are vectorisable and there are several steps.  Measured
+    // (same box, on / off): batch 4 836 / 814 img/s, 16: 2249 / 2211, 32: 3054 / 3014, 128: neutral; cfg5 86.0 / 84.2; the
+    // split-K weight gradients (layout 2) add +1 % at batch 4 and are neutral elsewhere
+    p.deep = !p.one_step && a.use_tr && a.fast && a.a_vec && a.b_vec && !POL(gemm_no_deep128) &&
+             (layout == 2 ? (M % 8 == 0 && N % 8 == 0) : (K % 8 == 0 && (layout == 0 || N % 8 == 0) && p.slices == 1));
+    return p;
+}
+
+// ---- one launch function per family (the trace names a kernel by the text of its launch statement: common.h) -------------------
+static int gemm_launch_streaming(const GemmPlan& p, int layout, hipStream_t st, const GemmArgs& a) {
+    bool ok = true;           // (gemm_skinny_nt / gemm_dw_skinny_plan only name instantiated forms)
+    if (p.family == GemmFamily::SkinnyRows) {
+        hipLaunchKernelGGL((gemm_skinny_rows_kernel<1, 6>), p.grid, dim3(256), 0, st, a);
+    } else if (p.family == GemmFamily::SkinnyK) {
+        const int ks = p.ks;
+        const unsigned gx = p.grid.x;
+        if (layout == 0) { if (a.N == 32) gemm_skinny_k_launch<0, 2>(ks, gx, st, a); else gemm_skinny_k_launch<0, 4>(ks, gx, st, a); }
+        else { if (a.N == 32) gemm_skinny_k_launch<1, 2>(ks, gx, st, a); else gemm_skinny_k_launch<1, 4>(ks, gx, st, a); }
+    } else if (p.family == GemmFamily::Skinny) {
+        ok = layout == 0 ? gemm_skinny_launch<0>(p.ks, p.nt, p.grid, st, a) : gemm_skinny_launch<1>(p.ks, p.nt, p.grid, st, a);
+    } else {
+        ok = p.sk.mt == 2 ? gemm_dw_skinny_launch_nt<2>(p.sk.nt, p.grid, st, a, p.sk.slices)
+           : p.sk.mt == 4 ? gemm_dw_skinny_launch_nt<4>(p.sk.nt, p.grid, st, a, p.sk.slices)
+                          : gemm_dw_skinny_launch_nt<8>(p.sk.nt, p.grid, st, a, p.sk.slices);
+    }
+    if (!ok) return SEGF_ERR_SHAPE;
+    SEGF_CHECK_LAUNCH();
+    return 0;
+}
+// (SEGF_ERR_SHAPE = the eight-phase launcher declined -- operand alignment it needs and the plan does not look at: gemm_impl re-plans)
+static int gemm_launch_eight(const GemmPlan& p, int layout, hipStream_t st, const GemmArgs& a) {
+    return gemm8_launch(layout, 0, 0, a.M, a.N, a.K, a.kchunk, p.slices, a.A, a.lda, a.B, a.ldb, a.C, a.ldc, 0, 0, 0, 1, nullptr, nullptr, a.bias,
+                        a.residual, a.ldr, a.rscale, a.rpg, a.ws, st);
+}
+#define LAUNCH_G(L)                                                                                              \
+    do {                                                                                                         \
+        if (f32o) hipLaunchKernelGGL((gemm_bf16_big_kernel<L, float, false>), gridb, dim3(GG_THREADS), 0, st, a);  \
+        else hipLaunchKernelGGL((gemm_bf16_big_kernel<L, bf16_t, false>), gridb, dim3(GG_THREADS), 0, st, a);      \
+    } while (0)
+static int gemm_launch_big(const GemmPlan& p, int layout, hipStream_t st, const GemmArgs& a) {
+    const dim3 gridb = p.grid;
+    const bool f32o = p.f32_out;
+    const bool narrow_n = p.narrow && layout == 0, narrow_n1 = p.narrow && layout == 1, narrow_m = p.narrow && layout == 2;
+    if (a.pro_scale) {
+        if (layout == 0 && !f32o) {
+            if (narrow_n && p.deep) hipLaunchKernelGGL((gemm_bf16_big_kernel<0, bf16_t, false, true, 1, true>), gridb, dim3(GG_THREADS), 0, st, a);
+            else if (narrow_n) hipLaunchKernelGGL((gemm_bf16_big_kernel<0, bf16_t, false, true, 1>), gridb, dim3(GG_THREADS), 0, st, a);
+            else hipLaunchKernelGGL((gemm_bf16_big_kernel<0, bf16_t, false, true>), gridb, dim3(GG_THREADS), 0, st, a);
+        } else if (layout == 2 && f32o) {
+            if (narrow_m) hipLaunchKernelGGL((gemm_bf16_big_kernel<2, float, false, true, 2>), gridb, dim3(GG_THREADS), 0, st, a);
+            else hipLaunchKernelGGL((gemm_bf16_big_kernel<2, float, false, true>), gridb, dim3(GG_THREADS), 0, st, a);
+        } else return SEGF_ERR_SHAPE;
+    } else if (narrow_n && p.deep) hipLaunchKernelGGL((gemm_bf16_big_kernel<0, bf16_t, false, false, 1, true>), gridb, dim3(GG_THREADS), 0, st, a);
+    else if (narrow_n) hipLaunchKernelGGL((gemm_bf16_big_kernel<0, bf16_t, false, false, 1>), gridb, dim3(GG_THREADS), 0, st, a);
+    else if (narrow_m) hipLaunchKernelGGL((gemm_bf16_big_kernel<2, float, false, false, 2>), gridb, dim3(GG_THREADS), 0, st, a);
+    else if (narrow_n1) hipLaunchKernelGGL((gemm_bf16_big_kernel<1, bf16_t, false, false, 1>), gridb, dim3(GG_THREADS), 0, st, a);
+    else if (layout == 0) LAUNCH_G(0); else if (layout == 1) LAUNCH_G(1); else LAUNCH_G(2);
+    SEGF_CHECK_LAUNCH();
+    return 0;
+}
+#undef LAUNCH_G
+#define LAUNCH_B(L, OT)                                                                                      \
+    do {                                                                                                     \
+        if (one_step && L != 2) hipLaunchKernelGGL((gemm_bf16_kernel<(L == 2 ? 0 : L), OT, true, false, 1>), grid, dim3(256), 0, st, a); \
+        else if (deep128) hipLaunchKernelGGL((gemm_bf16_kernel<L, OT, true, false, 2, true>), grid, dim3(256), 0, st, a); \
+        else if (L == 0 || a.use_tr) hipLaunchKernelGGL((gemm_bf16_kernel<L, OT, true>), grid, dim3(256), 0, st, a); \
+        else hipLaunchKernelGGL((gemm_bf16_kernel<L, OT, false>), grid, dim3(256), 0, st, a);                 \
+    } while (0)
+static int gemm_launch_tile128(const GemmPlan& p, int layout, hipStream_t st, const GemmArgs& a) {
+    const dim3 grid = p.grid;
+    const bool one_step = p.one_step, deep128 = p.deep;
+    if (p.f32_out) {
+        if (layout == 0) LAUNCH_B(0, float); else if (layout == 1) LAUNCH_B(1, float); else LAUNCH_B(2, float);
+    } else {
+        if (layout == 0) LAUNCH_B(0, bf16_t); else if (layout == 1) LAUNCH_B(1, bf16_t); else LAUNCH_B(2, bf16_t);
+    }
+    SEGF_CHECK_LAUNCH();
+    return 0;
+}
+#undef LAUNCH_B
+#define LAUNCH_FM(L)                                                                                          \
+    do {                                                                                                      \
+        if (narrow && tn == 1) hipLaunchKernelGGL((gemm_f32_mfma_kernel<L, 1, 1, 4>), gm, dim3(256), 0, st, a);      \
+        else if (narrow && tn == 2) hipLaunchKernelGGL((gemm_f32_mfma_kernel<L, 1, 2, 4>), gm, dim3(256), 0, st, a); \
+        else if (narrow && tn == 3) hipLaunchKernelGGL((gemm_f32_mfma_kernel<L, 1, 3, 4>), gm, dim3(256), 0, st, a); \
+        else if (narrow && tn == 4) hipLaunchKernelGGL((gemm_f32_mfma_kernel<L, 1, 4, 4>), gm, dim3(256), 0, st, a); \
+        else if (narrow) hipLaunchKernelGGL((gemm_f32_mfma_kernel<L, 1, 5, 4>), gm, dim3(256), 0, st, a);            \
+        else if (big) hipLaunchKernelGGL((gemm_f32_mfma_kernel<L, 2, 2>), gm, dim3(256), 0, st, a);           \
+        else hipLaunchKernelGGL((gemm_f32_mfma_kernel<L, 1, 1>), gm, dim3(256), 0, st, a);                    \
+    } while (0)
+static int gemm_launch_f32(const GemmPlan& p, int layout, hipStream_t st, const GemmArgs& a) {
+    if (p.family == GemmFamily::F32Mfma) {
+        const dim3 gm = p.grid;
+        const bool narrow = p.narrow, big = p.wide;
+        const int tn = p.nt;
+        if (layout == 0) LAUNCH_FM(0); else if (layout == 1) LAUNCH_FM(1); else LAUNCH_FM(2);
+    } else {
+        const dim3 grid = p.grid;
+        if (layout == 0) hipLaunchKernelGGL((gemm_f32_kernel<0>), grid, dim3(256), 0, st, a);
+        else if (layout == 1) hipLaunchKernelGGL((gemm_f32_kernel<1>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((gemm_f32_kernel<2>), grid, dim3(256), 0, st, a);
+    }
+    SEGF_CHECK_LAUNCH();
+    return 0;
+}
+#undef LAUNCH_FM
+static int gemm_launch(const GemmPlan& p, int layout, hipStream_t st, const GemmArgs& a) {
+    switch (p.family) {
+    case GemmFamily::None: return p.err;
+    case GemmFamily::Eight: return gemm_launch_eight(p, layout, st, a);
+    case GemmFamily::Big: return gemm_launch_big(p, layout, st, a);
+    case GemmFamily::Tile128: return gemm_launch_tile128(p, layout, st, a);
+    case GemmFamily::F32Mfma: case GemmFamily::F32Fma: return gemm_launch_f32(p, layout, st, a);
+    default: return gemm_launch_streaming(p, layout, st, a);
+    }
+}
+// the reduce pass behind a split-K product (the bias gradient's slices ride in the same launch); cs_n = entries of the bias gradient
+static int gemm_reduce_tail(hipStream_t st, const GemmArgs& a, int c_dt, int slices, int64_t cs_n) {
+    if (!a.ws) return 0;
+    if (c_dt == SEGF_F32 && reduce_group_add(g_reduce_sink, a.ws, slices, a.M, a.N, (float*)a.C, a.ldc, a.colsum_ws, a.colsum, cs_n)) return 0;
+    if (c_dt == SEGF_F32) splitk_reduce_launch<float>(st, a.ws, slices, a.M, a.N, (float*)a.C, a.ldc, a.colsum_ws, a.colsum, cs_n);
+    else splitk_reduce_launch<bf16_t>(st, a.ws, slices, a.M, a.N, (bf16_t*)a.C, a.ldc, a.colsum_ws, a.colsum, cs_n);
+    SEGF_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int segf_colsum(int dt, const void* x, int64_t ldx, int64_t rows, int64_t cols, float* out, float* ws, void* stream);
+extern "C" int64_t segf_colsum_ws(int64_t rows, int64_t cols);
+
+// colsum = where the bias gradient of a weight gradient goes: it rides on the product where the plan lets it, and takes a column-sum
+// pass of its own behind it where not (big-tile / eight-phase / fp32 kernels)
 static int gemm_impl(int dt, int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
                      int64_t ldb, void* C, int c_dt, int64_t ldc, const float* bias, const void* residual, int64_t ldr,
                      const float* rscale, int64_t rows_per_group, int split_k, float* ws, float* colsum, void* stream,
-                     const GemmPro* pro = nullptr);
+                     const GemmPro* pro = nullptr) {
+    if (M <= 0 || N <= 0) return 0;
+    if (K < 0 || layout < 0 || layout > 2) return SEGF_ERR_SHAPE;
+    if (dt != SEGF_F32 && dt != SEGF_BF16) return SEGF_ERR_DTYPE;
+    if (c_dt != SEGF_F32 && c_dt != SEGF_BF16) return SEGF_ERR_DTYPE;
+    if (dt == SEGF_F32 && c_dt != SEGF_F32) return SEGF_ERR_DTYPE;
+    if (split_k < 1) split_k = 1;
+    if (split_k > 1 && (bias || residual)) return SEGF_ERR_SHAPE;
+    if (split_k > 1 && !ws) return SEGF_ERR_WORKSPACE;
+    if (rscale && rows_per_group <= 0) return SEGF_ERR_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    GemmArgs a = gemm_args(dt, layout, M, N, K, A, lda, B, ldb, C, c_dt, ldc, bias, residual, ldr, rscale, rows_per_group,
+                           gemm_kchunk(dt, K, split_k), ws, colsum, pro);
+    GemmPlan p = gemm_plan(dt, c_dt, layout, a, split_k);
+    if (!p.colsum_rides) { a.colsum = nullptr; a.colsum_ws = nullptr; }
+    int rc = gemm_launch(p, layout, st, a);
+    if (rc == SEGF_ERR_SHAPE && p.family == GemmFamily::Eight) {
+        p = gemm_plan(dt, c_dt, layout, a, split_k, PLAN_NO_EIGHT);
+        rc = gemm_launch(p, layout, st, a);
+    }
+    if (rc) return rc;
+    rc = gemm_reduce_tail(st, a, c_dt, p.slices, M);
+    if (rc || !colsum || p.colsum_rides) return rc;
+    return segf_colsum(dt, A, lda, K, M, colsum, ws + (split_k > 1 ? (int64_t)split_k * M * N : 0), stream);
+}
 
 extern "C" int segf_gemm(int dt, int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
                          int64_t ldb, void* C, int c_dt, int64_t ldc, const float* bias, const void* residual, int64_t ldr,
@@ -2214,9 +2549,6 @@ extern "C" int segf_gemm(int dt, int layout, int64_t M, int64_t N, int64_t K, co
     return gemm_impl(dt, layout, M, N, K, A, lda, B, ldb, C, c_dt, ldc, bias, residual, ldr, rscale, rows_per_group, split_k, ws,
                      nullptr, stream);
 }
-
-extern "C" int segf_colsum(int dt, const void* x, int64_t ldx, int64_t rows, int64_t cols, float* out, float* ws, void* stream);
-extern "C" int64_t segf_colsum_ws(int64_t rows, int64_t cols);
 
 // weight gradient + bias gradient in one pass over dy:  C[M,N] = A^T B (layout 2),  dbias[m] = sum_k A(k, m)
 extern "C" int64_t segf_gemm_dw_db_ws(int64_t M, int64_t N, int64_t K, int split_k) {
@@ -2228,20 +2560,6 @@ extern "C" int64_t segf_gemm_dw_db_ws(int64_t M, int64_t N, int64_t K, int split
 extern "C" int segf_gemm_dw_db(int dt, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb,
                                void* C, int c_dt, int64_t ldc, int split_k, float* ws, float* dbias, void* stream) {
     if (!dbias || !ws) return SEGF_ERR_WORKSPACE;
-    if (split_k < 1) split_k = 1;
-    DwSkinny sk;
-    const bool skinny = dt == SEGF_BF16 && c_dt == SEGF_F32 && gemm_dw_skinny_plan(M, N, K, true, sk) && sk.slices == split_k &&
-                        (uintptr_t)A % 16 == 0 && (lda * 2) % 16 == 0 && (uintptr_t)B % 16 == 0 && (ldb * 2) % 16 == 0 &&
-                        !POL(gemm_no_tr);
-    // fused in the streaming kernel (all-ones fragment), in the 128-tile kernel (all-ones column when N leaves one free, extra
-    // MFMAs when it does not); the 256-tile kernel has no registers to spare for it
-    const bool fused = dt == SEGF_BF16 && c_dt == SEGF_F32 && (skinny || !(gemm_use_big(2, M, N, K) || dw_on_gemm8(M, N, K))) &&
-                       !POL(gemm_no_fused_db);
-    if (!fused) {       // big-tile / fp32 kernels: separate column reduction (still one C-ABI call)
-        const int rc = gemm_impl(dt, 2, M, N, K, A, lda, B, ldb, C, c_dt, ldc, nullptr, nullptr, 0, nullptr, 1, split_k, ws, nullptr, stream);
-        if (rc) return rc;
-        return segf_colsum(dt, A, lda, K, M, dbias, ws + (split_k > 1 ? (int64_t)split_k * M * N : 0), stream);
-    }
     return gemm_impl(dt, 2, M, N, K, A, lda, B, ldb, C, c_dt, ldc, nullptr, nullptr, 0, nullptr, 1, split_k, ws, dbias, stream);
 }
 
@@ -2252,6 +2570,11 @@ extern "C" int segf_gemm_dw_db(int dt, int64_t M, int64_t N, int64_t K, const vo
 // largest output (elements) of a member that alone would take the 256-tile kernel and still joins a group (measured flat between 256 K
 // and 4 M elements)
 static inline int64_t dw_group_big_max() { return 1024 * 1024; }
+// the arguments gemm_impl builds for one item's product
+static GemmArgs dw_item_args(int dt, const SegfDwItem& it, int64_t kchunk) {
+    return gemm_args(dt, 2, it.M, it.N, it.K, it.dy, it.lddy, it.x, it.ldx, it.dw, SEGF_F32, it.lddw, nullptr, nullptr, 0, nullptr, 1, kchunk,
+                     it.ws, it.db, nullptr);
+}
 extern "C" int segf_gemm_dw_db_grouped(int dt, int n, const SegfDwItem* items, void* stream) {
     if (n <= 0) return 0;
     if (!items) return SEGF_ERR_SHAPE;
@@ -2271,8 +2594,7 @@ extern "C" int segf_gemm_dw_db_grouped(int dt, int n, const SegfDwItem* items, v
         bool any_flag = false;
         for (int j = 0; j < npend; ++j) {
             const SegfDwItem& it = items[pend[j]];
-            const int split_k = it.split_k < 1 ? 1 : it.split_k;
-            kslice[j] = cdiv64(cdiv64(it.K, split_k), GB_BK) * GB_BK;
+            kslice[j] = gemm_kchunk(dt, it.K, it.split_k);
             any_flag |= it.shared_split != 0;
         }
         if (any_flag && !no_shared && npend > 1) {
@@ -2298,32 +2620,15 @@ extern "C" int segf_gemm_dw_db_grouped(int dt, int n, const SegfDwItem* items, v
         g.n = 0; r.n = 0; g.start[0] = 0; r.start[0] = 0;
         for (int j = 0; j < npend; ++j) {
             const SegfDwItem& it = items[pend[j]];
-            const int64_t M = it.M, N = it.N, K = it.K, kchunk = kslice[j];
-            const int slices = (int)cdiv64(K, kchunk);
-            // the arguments gemm_impl builds for this product (layout 2, fp32 output, split-K partials in ws, bias column riding)
-            GemmArgs a;
-            a.A = it.dy; a.B = it.x; a.C = it.dw; a.bias = nullptr; a.residual = nullptr; a.rscale = nullptr;
-            a.M = M; a.N = N; a.K = K; a.lda = it.lddy; a.ldb = it.ldx; a.ldc = it.lddw; a.ldr = 0; a.rpg = 1;
-            a.kchunk = kchunk; a.ws = it.ws;
-            a.a_vec = 1; a.b_vec = 1; a.fast = 1; a.xcd_slabs = POL(dw_no_xcd_slabs) ? 0 : 1;
-            a.c_vec = ((uintptr_t)it.dw % 16 == 0) && ((it.lddw * 4) % 16 == 0);
-            a.r_vec = 0; a.c_vec16 = a.c_vec;
-            a.use_tr = 1;
-            a.cH = a.cW = a.cC = 0; a.csign = 1;
-            a.colsum = it.db; a.colsum_ws = it.ws + (int64_t)slices * M * N;
-            a.pro_scale = nullptr; a.pro_shift = nullptr; a.pro_rpg = 1; a.pro_ld = 0; a.pro_act = 0;
-            a.f8_sa = nullptr; a.f8_sb = nullptr;
+            const int64_t M = it.M, N = it.N;
+            const GemmArgs a = dw_item_args(dt, it, kslice[j]);
+            const int slices = gemm_slices(it.K, kslice[j]);
             const unsigned gx = (unsigned)cdiv64(N, GB_BN), gy = (unsigned)cdiv64(M, GB_BM), gz = (unsigned)slices;
             const int k = g.n;
             g.m[k] = a; g.gx[k] = gx; g.gy[k] = gy; g.gz[k] = gz;
             g.start[k + 1] = g.start[k] + gx * gy * gz;
             ++g.n;
-            const int form = splitk_reduce_form(it.ws, M, N, it.dw, it.lddw);
-            const unsigned blocks = splitk_reduce_main_blocks(form, M * N), csb = splitk_reduce_cs_blocks(form, M);
-            r.wide[k] = form; r.split[k] = slices; r.ws[k] = it.ws; r.C[k] = it.dw; r.cs_ws[k] = a.colsum_ws; r.cs_out[k] = it.db;
-            r.M[k] = M; r.N[k] = N; r.ldc[k] = it.lddw; r.cs_n[k] = M; r.main_blocks[k] = blocks;
-            r.start[k + 1] = r.start[k] + blocks + csb;
-            ++r.n;
+            reduce_group_add(&r, it.ws, slices, M, N, it.dw, it.lddw, a.colsum_ws, it.db, M);
         }
         npend = 0;
         if (g.n == 1) {          // a lone member: the ordinary launch pair (same arithmetic)
@@ -2333,10 +2638,8 @@ extern "C" int segf_gemm_dw_db_grouped(int dt, int n, const SegfDwItem* items, v
             hipLaunchKernelGGL((gemm_bf16_dw_group_kernel<true>), dim3(g.start[g.n]), dim3(256), 0, st, g);
         }
         SEGF_CHECK_LAUNCH();
-        if (r.n > 0) {
-            hipLaunchKernelGGL(splitk_reduce_group_kernel, dim3(r.start[r.n]), dim3(256), 0, st, r);
-            SEGF_CHECK_LAUNCH();
-        }
+        hipLaunchKernelGGL(splitk_reduce_group_kernel, dim3(r.start[r.n]), dim3(256), 0, st, r);
+        SEGF_CHECK_LAUNCH();
         return 0;
     };
     ReduceGroup r2;
@@ -2350,23 +2653,26 @@ extern "C" int segf_gemm_dw_db_grouped(int dt, int n, const SegfDwItem* items, v
     };
     for (int i = 0; i < n; ++i) {
         const SegfDwItem& it = items[i];
-        int split_k = it.split_k < 1 ? 1 : it.split_k;
         const int64_t M = it.M, N = it.N, K = it.K;
-        DwSkinny sk;
-        const bool aligned = (uintptr_t)it.dy % 16 == 0 && (it.lddy * 2) % 16 == 0 && (uintptr_t)it.x % 16 == 0 && (it.ldx * 2) % 16 == 0;
-        const bool skinny = gemm_dw_skinny_plan(M, N, K, true, sk) && sk.slices == split_k && aligned;
-        const int64_t kchunk = cdiv64(cdiv64(K, split_k), GB_BK) * GB_BK;
-        const int slices = (int)cdiv64(K > 0 ? K : 1, kchunk > 0 ? kchunk : GB_BK);
-        const bool groupable = !no_group && dt == SEGF_BF16 && M > 0 && N > 0 && K > 0 && it.dw && it.db && it.ws && !skinny && aligned &&
-                               (!gemm_use_big(2, M, N, K) || (it.shared_split && M * N <= dw_group_big_max())) && !dw_on_gemm8(M, N, K) &&
-                               !POL(gemm_no_fused_db) && !POL(gemm_no_fastload) &&
-                               !POL(gemm_no_tr) && !POL(gemm_no_deep128) && M % 8 == 0 && N % 8 == 0 && slices > 1 && cdiv64(M, GB_BM) <= 65535;
-        // (a member that alone would take the 256-tile kernel + a separate column-sum pass -- the stage-3 / 4 layers at batch 128 -- joins the
-        // group too when it lets the library choose its split: one pass over dy for both gradients; batch 128 +0.5 %)
+        // a member of a group: the product that ALONE takes the two-steps-in-flight 128-tile split-K kernel with the bias column riding
+        bool groupable = false;
+        if (!no_group && M > 0 && N > 0 && K > 0 && it.dw && it.db && it.ws) {
+            const GemmArgs a = dw_item_args(dt, it, gemm_kchunk(dt, K, it.split_k));
+            GemmPlan p = gemm_plan(dt, SEGF_F32, 2, a, it.split_k);
+            unsigned skip = 0;
+            // THE EXCEPTION: a member that alone would take the 256-tile kernel + a separate column-sum pass -- the stage-3 / 4 layers at
+            // batch 128 -- joins the group too when it lets the library choose its split: one pass over dy for both gradients; batch 128
+            // +0.5 %.  It is planned as if the 256-tile kernel did not exist.
+            if (p.shape == TileShape::Big && it.shared_split && M * N <= dw_group_big_max()) skip |= PLAN_NO_BIG;
+            // (as found: a request that only ROUNDS to the streaming kernel's slice count joins the group; alone it takes that kernel)
+            if (p.family == GemmFamily::DwSkinny && p.sk.slices != it.split_k) skip |= PLAN_NO_DW_SKINNY;
+            if (skip) p = gemm_plan(dt, SEGF_F32, 2, a, it.split_k, skip);
+            groupable = p.family == GemmFamily::Tile128 && p.deep && p.colsum_rides && p.slices > 1;
+        }
         if (!groupable) {                        // (the items are independent of each other: no need to close the open group)
             // its product launches now; its reduce pass joins the others' in r2 (issued when full and at the end of the call)
             g_reduce_sink = no_group ? nullptr : &r2;
-            const int rc = segf_gemm_dw_db(dt, M, N, K, it.dy, it.lddy, it.x, it.ldx, it.dw, SEGF_F32, it.lddw, split_k, it.ws, it.db, stream);
+            const int rc = segf_gemm_dw_db(dt, M, N, K, it.dy, it.lddy, it.x, it.ldx, it.dw, SEGF_F32, it.lddw, it.split_k, it.ws, it.db, stream);
             g_reduce_sink = nullptr;
             if (rc) return rc;
             if (r2.n == GDW_MAX) { const int rc2 = flush2(); if (rc2) return rc2; }
@@ -2402,227 +2708,6 @@ extern "C" int segf_gemm_pro(int dt, int layout, int64_t M, int64_t N, int64_t K
     return gemm_impl(dt, layout, M, N, K, A, lda, B, ldb, C, c_dt, ldc, bias, nullptr, 0, nullptr, 1, split_k, ws, nullptr, stream, &pro);
 }
 
-static int gemm_impl(int dt, int layout, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
-                     int64_t ldb, void* C, int c_dt, int64_t ldc, const float* bias, const void* residual, int64_t ldr,
-                     const float* rscale, int64_t rows_per_group, int split_k, float* ws, float* colsum, void* stream,
-                     const GemmPro* pro) {
-    if (M <= 0 || N <= 0) return 0;
-    if (K < 0 || layout < 0 || layout > 2) return SEGF_ERR_SHAPE;
-    if (dt != SEGF_F32 && dt != SEGF_BF16) return SEGF_ERR_DTYPE;
-    if (c_dt != SEGF_F32 && c_dt != SEGF_BF16) return SEGF_ERR_DTYPE;
-    if (dt == SEGF_F32 && c_dt != SEGF_F32) return SEGF_ERR_DTYPE;
-    if (split_k < 1) split_k = 1;
-    if (split_k > 1 && (bias || residual)) return SEGF_ERR_SHAPE;
-    if (split_k > 1 && !ws) return SEGF_ERR_WORKSPACE;
-    if (rscale && rows_per_group <= 0) return SEGF_ERR_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    GemmArgs a;
-    a.A = A; a.B = B; a.C = C; a.bias = bias; a.residual = residual; a.rscale = rscale;
-    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldr = ldr; a.rpg = rows_per_group > 0 ? rows_per_group : 1;
-    const int64_t kstep = dt == SEGF_BF16 ? GB_BK : GF_BK;
-    int64_t kchunk = cdiv64(cdiv64(K, split_k), kstep) * kstep;
-    if (kchunk <= 0) kchunk = kstep;
-    split_k = (int)cdiv64(K > 0 ? K : 1, kchunk);
-    a.kchunk = kchunk;
-    a.ws = split_k > 1 ? ws : nullptr;
-    const size_t esz = dt == SEGF_BF16 ? 2 : 4, csz = c_dt == SEGF_BF16 ? 2 : 4;
-    a.a_vec = ((uintptr_t)A % 16 == 0) && ((lda * esz) % 16 == 0);
-    a.b_vec = ((uintptr_t)B % 16 == 0) && ((ldb * esz) % 16 == 0);
-    a.fast = POL(gemm_no_fastload) ? 0 : 1;
-    a.xcd_slabs = (layout == 2 && split_k > 1 && !POL(dw_no_xcd_slabs)) ? 1 : 0;
-    // bit 0: vector loads allowed, bit 1: guard-free full-K-step loads.  Layouts 0 / 1 gain 25-45 % from the latter; the split-K
-    // weight-gradient launches (layout 2) measured 8-15 % SLOWER with every load in flight, so they keep the guarded loads
-    if (a.fast && layout != 2) { a.a_vec *= 3; a.b_vec *= 3; }
-    a.c_vec = ((uintptr_t)C % (4 * csz) == 0) && ((ldc * csz) % (4 * csz) == 0);
-    a.r_vec = residual ? (((uintptr_t)residual % 16 == 0) && ((ldr * esz) % 16 == 0)) : 0;
-    a.c_vec16 = ((uintptr_t)C % 16 == 0) && ((ldc * csz) % 16 == 0);
-    a.cH = a.cW = a.cC = 0; a.csign = 1;
-    a.colsum = colsum;
-    a.colsum_ws = (colsum && split_k > 1) ? ws + (int64_t)split_k * M * N : nullptr;
-    a.pro_scale = pro ? pro->scale : nullptr; a.pro_shift = pro ? pro->shift : nullptr;
-    a.pro_rpg = pro ? pro->rpg : 1; a.pro_ld = pro ? pro->ld : 0; a.pro_act = pro ? pro->act : 0;
-    a.f8_sa = nullptr; a.f8_sb = nullptr;
-    a.use_tr = POL(gemm_no_tr) ? 0 : 1;      // debugging switch: transposed fragments by scalar LDS loads instead of ds_read_b64_tr_b16
-    if (dt == SEGF_BF16) {
-        if (!pro && c_dt == SEGF_BF16 && split_k == 1 && a.a_vec && a.c_vec16 && (!residual || a.r_vec) &&
-            (layout == 1 || a.b_vec) && !POL(gemm_no_skinny)) {
-            if (layout == 0 && !residual && K == 32 && N == 768 && M >= 65536 && a.b_vec && !POL(gemm_no_skinny_rows)) {
-                const int64_t groups = cdiv64(M, 16);
-                int64_t gx = cdiv64(groups, 4 * 8);
-                if (gx > 1024) gx = 1024;
-                hipLaunchKernelGGL((gemm_skinny_rows_kernel<1, 6>), dim3((unsigned)gx), dim3(256), 0, st, a);
-                SEGF_CHECK_LAUNCH();
-                return 0;
-            }
-            if (gemm_skinny_k_ok(layout, M, N, K) && ldc % 4 == 0 && (!residual || ldr % 2 == 0)) {
-                const int64_t groups = cdiv64(M, 16);
-                const unsigned gx = (unsigned)imin64(groups, 256 * 12);     // several rounds of 16-token groups per workgroup
-                const int ks = (int)(K / 128);
-                if (layout == 0) { if (N == 32) gemm_skinny_k_launch<0, 2>(ks, gx, st, a); else gemm_skinny_k_launch<0, 4>(ks, gx, st, a); }
-                else { if (N == 32) gemm_skinny_k_launch<1, 2>(ks, gx, st, a); else gemm_skinny_k_launch<1, 4>(ks, gx, st, a); }
-                SEGF_CHECK_LAUNCH();
-                return 0;
-            }
-            const int nt = gemm_skinny_nt(layout, M, N, K);
-            if (nt) {
-                const int64_t groups = cdiv64(M, 16);
-                int64_t gx = cdiv64(groups, 4 * 4);           // >= 4 token groups per wave
-                if (gx > 2048) gx = 2048;
-                const dim3 grid((unsigned)gx, (unsigned)(N / (16 * nt)));
-                const bool ok = layout == 0 ? gemm_skinny_launch<0>((int)(K / 32), nt, grid, st, a)
-                                            : gemm_skinny_launch<1>((int)(K / 32), nt, grid, st, a);
-                if (ok) { SEGF_CHECK_LAUNCH(); return 0; }
-            }
-        }
-        if (layout == 2 && !pro && a.ws && c_dt == SEGF_F32 && a.use_tr && (a.a_vec & 1) && (a.b_vec & 1) && !bias && !residual) {
-            DwSkinny p;
-            // the caller sized ws for split_k slices (segf_gemm_pick_splitk gives this kernel's count): take it only then
-            if (gemm_dw_skinny_plan(M, N, K, true, p) && p.slices == split_k && kchunk % 32 == 0 && lda * 2 * 32 < (1ll << 31) && ldb * 2 * 32 < (1ll << 31)) {
-                if (!colsum) { a.colsum = nullptr; a.colsum_ws = nullptr; }
-                const dim3 gridk((unsigned)((p.slices + 3) / 4), (unsigned)p.colblocks, (unsigned)p.rowblocks);
-                const bool ok = p.mt == 2 ? gemm_dw_skinny_launch_nt<2>(p.nt, gridk, st, a, p.slices)
-                              : p.mt == 4 ? gemm_dw_skinny_launch_nt<4>(p.nt, gridk, st, a, p.slices)
-                                          : gemm_dw_skinny_launch_nt<8>(p.nt, gridk, st, a, p.slices);
-                if (ok) { SEGF_CHECK_LAUNCH(); goto reduce; }
-            }
-        }
-        // the eight-phase tile (gemm8.hip) for nn.Linear products with plain epilogues.  r03 measured it as a loss on every BASELINE model
-        // (12-load prologue, drain, direct 8-byte stores against 4 .. 48 K tiles); after the read-section diet of r05 it wins wherever it
-        // has >= 192 tiles to run, from K = 256 on, ragged last tiles included (tools/probe/linear8_probe.py, same process, us:
-        // [12800 x 3072] K = 768 102 -> 84; [12800 x 768] K = 3072 (150 tiles) 98 -> 69; [51200 x 384] K = 1536 (75 % of the launched tiles
-        // are output) 108 -> 77; [131072 x 320] K = 1280 (62.5 %) 219 -> 152; [131072 x 1280] K = 320 220 -> 197; [3200 x 6144] K = 1536
-        // 106 -> 80; [32768 x 512] K = 2048 74 -> 57 = 1.21 PFLOP/s).  Not taken: fewer than 128 tiles (78 .. 96 tiles: -2 .. +6 %), and
-        // 128 .. 191 tiles unless K >= 2048.  SEGFAC_GEMM8_LINEAR=0 switches it off (cfg5 101.8 -> 98.9 images/s, same box).
-        if (!pro && a.use_tr && !colsum && (a.a_vec & 1) && (a.b_vec & 1) && POL(gemm8_linear) && M > 128 && N > 128) {
-            const bool f32o8 = c_dt == SEGF_F32 || a.ws;
-            // whole-tile count the launch pays for, and the share of it that is output (ragged last tiles: [51200 x 384] = 75 %)
-            const int64_t tiles8 = cdiv64(M, 256) * cdiv64(N, 256);
-            const bool dense = 100 * M * N >= (int64_t)POL(gemm8_linear_min_fill) * tiles8 * 65536;
-            // ... and only where the gain pays for what a launch of this kernel costs the kernels AFTER it (in-situ traces of the cfg2 / cfg4
-            // step, tools/probe/trace_ab.sh: the launches that followed an eight-phase launch ran 3 - 10 % longer -- the chip gives clock back
-            // after the dense MFMA burst -- ~10 us per launch summed over the step): the gain is ~20 - 30 % of the product's time, i.e. worth it
-            // from ~36 GFLOP on (K >= 512) and, for the 4 - 7 K tiles of a shorter reduction, from ~100 GFLOP on.
-            const double gflop = 2e-9 * (double)M * (double)N * (double)K;
-            const bool worth = gflop >= (K >= 512 ? (double)POL(gemm8_linear_min_gflop) : 100.0);
-            const bool fits = K >= POL(gemm8_linear_min_k) && dense && worth && (tiles8 >= 192 || (tiles8 >= POL(gemm8_linear_min_tiles) && K >= 2048));
-            if (layout != 2 && fits && !f32o8 && split_k == 1 && gemm8_linear_ok(M, N, K, a.kchunk) && (!residual || a.r_vec)) {
-                const int rc8 = gemm8_launch(layout, 0, 0, M, N, K, a.kchunk, 1, A, lda, B, ldb, C, ldc, 0, 0, 0, 1, nullptr, nullptr, bias, residual,
-                                             ldr, rscale, a.rpg, nullptr, st);
-                if (rc8 != SEGF_ERR_SHAPE) return rc8;
-            }
-            if (layout == 2 && (gemm_use_big(layout, M, N, K) || dw_on_gemm8(M, N, K)) && c_dt == SEGF_F32 && !bias && !residual &&
-                gemm8_supported(2, 0, M, N, K, a.kchunk, 0)) {
-                const int rc8 = gemm8_launch(2, 0, 0, M, N, K, a.kchunk, split_k, A, lda, B, ldb, C, ldc, 0, 0, 0, 1, nullptr, nullptr, nullptr,
-                                             nullptr, 0, nullptr, 1, a.ws, st);
-                if (rc8 != SEGF_ERR_SHAPE) { if (rc8) return rc8; goto reduce; }
-            }
-        }
-        // short reductions (K <= 704: the MiT stage-3 / 4 linears at 160 / 640 / 256) stay on the 128-tile kernel: with a handful of K
-        // steps the 256-tile kernel's operand reuse buys nothing (the product is bound by its output) and its one workgroup per CU
-        // exposes every load -> LDS -> MFMA round trip; two workgroups per CU with two K steps in flight: cfg2 +0.4 %, batch 16
-        // +0.7 %, cfg4 +0.2 % (same box).  The narrow shapes (N <= 160) keep their one-tile kernel; the implicit-GEMM convolutions
-        // (other entry points) are not concerned.
-        const int smallk = 704;
-        const bool short_k = layout != 2 && K <= smallk && N > 160 && !pro;
-        if (((gemm_use_big(layout, M, N, K) && !short_k) || pro) && a.use_tr) {
-            dim3 gridb((unsigned)cdiv64(N, GG_B), (unsigned)cdiv64(M, GG_B), (unsigned)split_k);
-            if (gridb.y > 65535u) return SEGF_ERR_SHAPE;
-            const bool f32o = c_dt == SEGF_F32 || a.ws;
-#define LAUNCH_G(L)                                                                                              \
-    do {                                                                                                         \
-        if (f32o) hipLaunchKernelGGL((gemm_bf16_big_kernel<L, float, false>), gridb, dim3(GG_THREADS), 0, st, a);  \
-        else hipLaunchKernelGGL((gemm_bf16_big_kernel<L, bf16_t, false>), gridb, dim3(GG_THREADS), 0, st, a);      \
-    } while (0)
-            // partly filled workgroup tiles: the narrow wave shapes (see the kernel's header)
-            const bool narrow_n = layout == 0 && !f32o && N <= 160 && !POL(gemm_no_narrow);
-            const bool narrow_n1 = layout == 1 && !f32o && !a.pro_scale && N <= 160 && !POL(gemm_no_narrow);
-            const bool narrow_m = layout == 2 && f32o && M <= 160 && !POL(gemm_no_narrow);
-            const bool deep = layout == 0 && split_k == 1 && (a.a_vec & 2) && (a.b_vec & 2) && K % GB_BK == 0 && K >= 2 * GB_BK &&
-                              (!a.pro_scale || a.pro_ld <= 1024) && !POL(gemm_no_deep);
-            if (a.pro_scale) {
-                if (layout == 0 && !f32o) {
-                    if (narrow_n && deep) hipLaunchKernelGGL((gemm_bf16_big_kernel<0, bf16_t, false, true, 1, true>), gridb, dim3(GG_THREADS), 0, st, a);
-                    else if (narrow_n) hipLaunchKernelGGL((gemm_bf16_big_kernel<0, bf16_t, false, true, 1>), gridb, dim3(GG_THREADS), 0, st, a);
-                    else hipLaunchKernelGGL((gemm_bf16_big_kernel<0, bf16_t, false, true>), gridb, dim3(GG_THREADS), 0, st, a);
-                } else if (layout == 2 && f32o) {
-                    if (narrow_m) hipLaunchKernelGGL((gemm_bf16_big_kernel<2, float, false, true, 2>), gridb, dim3(GG_THREADS), 0, st, a);
-                    else hipLaunchKernelGGL((gemm_bf16_big_kernel<2, float, false, true>), gridb, dim3(GG_THREADS), 0, st, a);
-                } else return SEGF_ERR_SHAPE;
-            } else if (narrow_n && deep) hipLaunchKernelGGL((gemm_bf16_big_kernel<0, bf16_t, false, false, 1, true>), gridb, dim3(GG_THREADS), 0, st, a);
-            else if (narrow_n) hipLaunchKernelGGL((gemm_bf16_big_kernel<0, bf16_t, false, false, 1>), gridb, dim3(GG_THREADS), 0, st, a);
-            else if (narrow_m) hipLaunchKernelGGL((gemm_bf16_big_kernel<2, float, false, false, 2>), gridb, dim3(GG_THREADS), 0, st, a);
-            else if (narrow_n1) hipLaunchKernelGGL((gemm_bf16_big_kernel<1, bf16_t, false, false, 1>), gridb, dim3(GG_THREADS), 0, st, a);
-            else
-            if (layout == 0) LAUNCH_G(0); else if (layout == 1) LAUNCH_G(1); else LAUNCH_G(2);
-#undef LAUNCH_G
-            SEGF_CHECK_LAUNCH();
-            goto reduce;
-        }
-        if (pro) return SEGF_ERR_SHAPE;            // only the 256-tile kernel applies operand prologues
-        dim3 grid((unsigned)cdiv64(N, GB_BN), (unsigned)cdiv64(M, GB_BM), (unsigned)split_k);
-        if (grid.y > 65535u) return SEGF_ERR_SHAPE;
-        const bool one_step = kchunk <= GB_BK && layout != 2;     // single K step: the 34 KB single-buffer variant
-        // two K steps in flight (branch-free loaders) whenever the operands are vectorisable and there are several steps.  Measured
-        // (same box, on / off): batch 4 836 / 814 img/s, 16: 2249 / 2211, 32: 3054 / 3014, 128: neutral; cfg5 86.0 / 84.2; the
-        // split-K weight gradients (layout 2) add +1 % at batch 4 and are neutral elsewhere
-        const bool vec_ab = a.a_vec && a.b_vec;
-        const bool deep128 = !one_step && a.use_tr && a.fast && vec_ab && !POL(gemm_no_deep128) &&
-                             (layout == 2 ? (M % 8 == 0 && N % 8 == 0)
-                                          : (K % 8 == 0 && (layout == 0 || N % 8 == 0) && split_k == 1));
-#define LAUNCH_B(L, OT)                                                                                      \
-    do {                                                                                                     \
-        if (one_step && L != 2) hipLaunchKernelGGL((gemm_bf16_kernel<(L == 2 ? 0 : L), OT, true, false, 1>), grid, dim3(256), 0, st, a); \
-        else if (deep128) hipLaunchKernelGGL((gemm_bf16_kernel<L, OT, true, false, 2, true>), grid, dim3(256), 0, st, a); \
-        else if (L == 0 || a.use_tr) hipLaunchKernelGGL((gemm_bf16_kernel<L, OT, true>), grid, dim3(256), 0, st, a); \
-        else hipLaunchKernelGGL((gemm_bf16_kernel<L, OT, false>), grid, dim3(256), 0, st, a);                 \
-    } while (0)
-        if (c_dt == SEGF_F32 || a.ws) {
-            if (layout == 0) LAUNCH_B(0, float); else if (layout == 1) LAUNCH_B(1, float); else LAUNCH_B(2, float);
-        } else {
-            if (layout == 0) LAUNCH_B(0, bf16_t); else if (layout == 1) LAUNCH_B(1, bf16_t); else LAUNCH_B(2, bf16_t);
-        }
-#undef LAUNCH_B
-    } else {
-        dim3 grid((unsigned)cdiv64(N, GF_BN), (unsigned)cdiv64(M, GF_BM), (unsigned)split_k);
-        if (grid.y > 65535u) return SEGF_ERR_SHAPE;
-        if (!POL(gemm_f32_no_mfma)) {               // exact fp32 on the matrix pipe
-            // 128 x 128 tiles when they still give every CU a workgroup (or the output is so large that operand traffic decides); a
-            // narrow output (N <= 160) over many rows in ONE column tile of 128 x (32 TN); 64 x 64 otherwise
-            const int64_t big_tiles = cdiv64(M, 128) * cdiv64(N, 128) * split_k;
-            const bool narrow = N <= 160 && cdiv64(M, 128) * split_k >= 192;
-            const int tn = (int)cdiv64(N, 32);
-            const bool big = !narrow && M >= 128 && N >= 96 && big_tiles >= 192;
-            const dim3 gm((unsigned)(narrow ? 1 : cdiv64(N, big ? 128 : 64)), (unsigned)cdiv64(M, (big || narrow) ? 128 : 64), (unsigned)split_k);
-            if (gm.y > 65535u) return SEGF_ERR_SHAPE;
-#define LAUNCH_FM(L)                                                                                          \
-    do {                                                                                                      \
-        if (narrow && tn == 1) hipLaunchKernelGGL((gemm_f32_mfma_kernel<L, 1, 1, 4>), gm, dim3(256), 0, st, a);      \
-        else if (narrow && tn == 2) hipLaunchKernelGGL((gemm_f32_mfma_kernel<L, 1, 2, 4>), gm, dim3(256), 0, st, a); \
-        else if (narrow && tn == 3) hipLaunchKernelGGL((gemm_f32_mfma_kernel<L, 1, 3, 4>), gm, dim3(256), 0, st, a); \
-        else if (narrow && tn == 4) hipLaunchKernelGGL((gemm_f32_mfma_kernel<L, 1, 4, 4>), gm, dim3(256), 0, st, a); \
-        else if (narrow) hipLaunchKernelGGL((gemm_f32_mfma_kernel<L, 1, 5, 4>), gm, dim3(256), 0, st, a);            \
-        else if (big) hipLaunchKernelGGL((gemm_f32_mfma_kernel<L, 2, 2>), gm, dim3(256), 0, st, a);           \
-        else hipLaunchKernelGGL((gemm_f32_mfma_kernel<L, 1, 1>), gm, dim3(256), 0, st, a);                    \
-    } while (0)
-            if (layout == 0) LAUNCH_FM(0); else if (layout == 1) LAUNCH_FM(1); else LAUNCH_FM(2);
-#undef LAUNCH_FM
-        } else
-        if (layout == 0) hipLaunchKernelGGL((gemm_f32_kernel<0>), grid, dim3(256), 0, st, a);
-        else if (layout == 1) hipLaunchKernelGGL((gemm_f32_kernel<1>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((gemm_f32_kernel<2>), grid, dim3(256), 0, st, a);
-    }
-    SEGF_CHECK_LAUNCH();
-reduce:
-    if (a.ws) {
-        // (the bias gradient's slices ride in the same launch)
-        if (c_dt == SEGF_F32 && reduce_sink_take(ws, split_k, M, N, (float*)C, ldc, a.colsum_ws, a.colsum, M)) return 0;
-        if (c_dt == SEGF_F32) splitk_reduce_launch<float>(st, ws, split_k, M, N, (float*)C, ldc, a.colsum_ws, a.colsum, M);
-        else splitk_reduce_launch<bf16_t>(st, ws, split_k, M, N, (bf16_t*)C, ldc, a.colsum_ws, a.colsum, M);
-        SEGF_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
 
 // ---- 3x3 convolution (stride 1, pad 1) on NHWC as an implicit GEMM: no im2col matrix is materialised -------------------------
 // reference: ConvModule(.., 3, 1, 1) of models/heads/upernet.py:26,28, models/modules/ppm.py:19, models/heads/fpn.py:19.
@@ -2632,10 +2717,22 @@ reduce:
 // P = B*H*W.  bf16 only (the fp32 parity mode goes through segf_im2col + segf_gemm).  Channel counts must be multiples of 8.
 // The 3x3 weight gradient has a LARGE output (Cout x 9 Cin: 81 tiles of 256^2 at 768 -> 768) even where its reduction is short (the
 // 32^2 .. 80^2 maps of UPerHead's FPN, upernet.py:26-28): the eight-phase tile with a few slices then beats the 128-tile kernel that
-// gemm_use_big's token-count rule (made for the small outputs of nn.Linear) sends it to -- [8 x 80 x 80, 768 -> 768]: 381 -> 577 TFLOP/s.
+// the token-count rule of gemm_tile_shape (made for the small outputs of nn.Linear) sends it to -- [8 x 80 x 80, 768 -> 768]: 381 -> 577 TFLOP/s.
 static inline bool conv3x3_wgrad_big(int64_t M, int64_t N, int64_t K) {
-    if (gemm_use_big(2, M, N, K)) return true;
+    if (gemm_tile_shape(2, M, N, K) == TileShape::Big) return true;
     return !POL(gemm_no_big) && M % 256 == 0 && N % 256 == 0 && (M / 256) * (N / 256) >= 48 && K >= 4096;
+}
+// Slices (first .. 8, of at least min_steps K steps each) for `tiles` 256 x 256 tiles: each count that fills the last round of 256
+// workgroups better than the best so far (fill0 to begin with) by more than `gain` is taken, up to the first that fills it >= 90 %
+static int conv_fill_slices(int64_t tiles, int64_t K, int first, int min_steps, double fill0, double gain) {
+    int best = 1;
+    for (int c = first; c <= 8 && K / c >= min_steps * 64; ++c) {
+        const int64_t wg = tiles * c;
+        const double u = (double)wg / (double)(cdiv64(wg, 256) * 256);
+        if (u > fill0 + gain) { fill0 = u; best = c; }
+        if (u >= 0.9) break;
+    }
+    return best;
 }
 // Forward / data gradient of a 3x3 convolution whose output has too few 256 x 256 tiles to fill the chip but a long reduction (UPerHead's PPM
 // bottleneck 3840 -> 768 on a 16 x 16 map, ppm.py:19: 96 tiles at batch 32; the 40 x 40 / 20 x 20 levels of cfg5): split the (channel block,
@@ -2647,33 +2744,13 @@ extern "C" int segf_conv3x3_fwd_splitk(int mode, int B, int H, int W, int Cin, i
     if (N % 256 || Kc % 64 || M <= 0) return 1;                  // (any pixel count: the last row tile may be ragged)
     const int64_t tiles = cdiv64(M, 256) * (N / 256);
     if (tiles >= 160 || K < 4096) return 1;
-    int best = 1;
-    double bu = (double)tiles / 256.0;
-    for (int c = 2; c <= 8; ++c) {
-        if (K / c < 24 * 64) break;                     // slices of at least 24 K steps
-        const int64_t wg = tiles * c;
-        const double u = (double)wg / (double)(cdiv64(wg, 256) * 256);
-        if (u > bu + 0.05) { bu = u; best = c; }
-        if (u >= 0.9) break;
-    }
-    return best;
+    return conv_fill_slices(tiles, K, 2, 24, (double)tiles / 256.0, 0.05);
 }
 // split-K count for segf_conv3x3 mode 2 (the caller sizes ws with it)
 extern "C" int segf_conv3x3_pick_splitk(int Cin, int Cout, int64_t P) {
     const int64_t M = Cout, N = 9 * (int64_t)Cin;
-    if (gemm_use_big(2, M, N, P) || !conv3x3_wgrad_big(M, N, P)) return segf_gemm_pick_splitk(M, N, P);
-    // fewest slices (<= 8) whose last round of 256 workgroups is >= 90 % full, slices of at least 16 K steps
-    const int64_t tiles = (M / 256) * (N / 256);
-    int best = 1;
-    double bu = 0.0;
-    for (int c = 1; c <= 8; ++c) {
-        if (P / c < 16 * 64) break;
-        const int64_t wg = tiles * c;
-        const double u = (double)wg / (double)(cdiv64(wg, 256) * 256);
-        if (u > bu + 0.02) { bu = u; best = c; }
-        if (u >= 0.9) break;
-    }
-    return best;
+    if (gemm_tile_shape(2, M, N, P) == TileShape::Big || !conv3x3_wgrad_big(M, N, P)) return segf_gemm_pick_splitk(M, N, P);
+    return conv_fill_slices((M / 256) * (N / 256), P, 1, 16, 0.0, 0.02);
 }
 extern "C" int segf_conv3x3(int mode, int B, int H, int W, int Cin, int Cout, const void* x, int64_t ldx, const void* w, int64_t ldw,
                             void* y, int y_dt, int64_t ldy, const float* bias, int split_k, float* ws, void* stream) {
@@ -2684,11 +2761,9 @@ extern "C" int segf_conv3x3(int mode, int B, int H, int W, int Cin, int Cout, co
     hipStream_t st = (hipStream_t)stream;
     const int64_t P = (int64_t)B * H * W;
     GemmArgs a;
-    a.bias = bias; a.residual = nullptr; a.rscale = nullptr; a.ldr = 0; a.rpg = 1;
-    a.a_vec = 1; a.b_vec = 1; a.r_vec = 0; a.use_tr = 1;
+    a.bias = bias;
+    a.a_vec = 1; a.b_vec = 1; a.use_tr = 1;
     a.cH = H; a.cW = W; a.csign = mode == 1 ? -1 : 1;
-    a.colsum = nullptr; a.colsum_ws = nullptr; a.pro_scale = nullptr; a.pro_shift = nullptr; a.pro_rpg = 1; a.pro_ld = 0; a.pro_act = 0;
-    a.f8_sa = nullptr; a.f8_sb = nullptr;
     int layout;
     if (mode == 0) { layout = 0; a.M = P; a.N = Cout; a.K = 9 * (int64_t)Cin; a.A = x; a.lda = ldx; a.B = w; a.ldb = ldw; a.cC = Cin; }
     else if (mode == 1) { layout = 0; a.M = P; a.N = Cin; a.K = 9 * (int64_t)Cout; a.A = x; a.lda = ldx; a.B = w; a.ldb = ldw; a.cC = Cout; }
@@ -2699,61 +2774,39 @@ extern "C" int segf_conv3x3(int mode, int B, int H, int W, int Cin, int Cout, co
     // forward / data gradient: split-K only in the form segf_conv3x3_fwd_splitk proposes (few output tiles, long reduction)
     if (mode != 2 && !(split_k > 1 && ws && y_dt == SEGF_BF16 && !bias && split_k == segf_conv3x3_fwd_splitk(mode, B, H, W, Cin, Cout))) split_k = 1;
     if (split_k > 1 && !ws) return SEGF_ERR_WORKSPACE;
-    int64_t kchunk = cdiv64(cdiv64(a.K, split_k), GB_BK) * GB_BK;
-    split_k = (int)cdiv64(a.K, kchunk);
-    a.kchunk = kchunk;
+    a.kchunk = gemm_kchunk(SEGF_BF16, a.K, split_k);
+    split_k = gemm_slices(a.K, a.kchunk);
     a.ws = split_k > 1 ? ws : nullptr;
     const size_t csz = y_dt == SEGF_BF16 ? 2 : 4;
     a.c_vec = ((uintptr_t)y % (4 * csz) == 0) && ((ldy * csz) % (4 * csz) == 0);
     a.c_vec16 = ((uintptr_t)y % 16 == 0) && ((ldy * csz) % 16 == 0);
     const bool f32out = y_dt == SEGF_F32 || a.ws;
-    if (layout == 0 && mode != 2 && a.ws) {      // the few-tiles form: eight-phase tiles over K slices, fp32 partials, one reduce to bf16
-        const int rc8 = gemm8_launch(0, 1, 0, a.M, a.N, a.K, a.kchunk, split_k, a.A, a.lda, a.B, a.ldb, y, ldy, H, W, a.cC, a.csign, nullptr, nullptr,
-                                     nullptr, nullptr, 0, nullptr, 1, a.ws, st);
+    // the eight-phase tile: the few-tiles form of the forward / data gradient (K slices, fp32 partials, one reduce to bf16), the bf16
+    // forward / data gradient where it has the tiles, the weight gradient with a large output
+    const bool eight = layout == 0 ? a.ws || (!f32out && gemm8_supported(0, 1, a.M, a.N, a.K, a.kchunk, a.cC))
+                                   : y_dt == SEGF_F32 && conv3x3_wgrad_big(a.M, a.N, a.K) && gemm8_supported(2, 1, a.M, a.N, a.K, a.kchunk, a.cC);
+    if (eight) {
+        const int rc8 = gemm8_launch(layout, 1, 0, a.M, a.N, a.K, a.kchunk, split_k, a.A, a.lda, a.B, a.ldb, y, ldy, H, W, a.cC, a.csign, nullptr, nullptr,
+                                     bias, nullptr, 0, nullptr, 1, a.ws, st);
         if (rc8) return rc8;
-        goto reduce3;
-    }
-    if (layout == 0 && !f32out && gemm8_supported(0, 1, a.M, a.N, a.K, a.kchunk, a.cC))
-        return gemm8_launch(0, 1, 0, a.M, a.N, a.K, a.kchunk, 1, a.A, a.lda, a.B, a.ldb, y, ldy, H, W, a.cC, a.csign, nullptr, nullptr, bias,
-                            nullptr, 0, nullptr, 1, nullptr, st);
-    if (layout == 2 && y_dt == SEGF_F32 && conv3x3_wgrad_big(a.M, a.N, a.K) && gemm8_supported(2, 1, a.M, a.N, a.K, a.kchunk, a.cC)) {
-        const int rc8 = gemm8_launch(2, 1, 0, a.M, a.N, a.K, a.kchunk, split_k, a.A, a.lda, a.B, a.ldb, y, ldy, H, W, a.cC, 1, nullptr, nullptr,
-                                     nullptr, nullptr, 0, nullptr, 1, a.ws, st);
-        if (rc8) return rc8;
-        goto reduce3;
-    }
-    if (gemm_use_big(layout, a.M, a.N, a.K)) {
+    } else if (gemm_tile_shape(layout, a.M, a.N, a.K) == TileShape::Big) {
         dim3 gridb((unsigned)cdiv64(a.N, GG_B), (unsigned)cdiv64(a.M, GG_B), (unsigned)split_k);
         if (gridb.y > 65535u) return SEGF_ERR_SHAPE;
-        if (layout == 0) {
-            if (f32out) hipLaunchKernelGGL((gemm_bf16_big_kernel<0, float, true>), gridb, dim3(GG_THREADS), 0, st, a);
-            else hipLaunchKernelGGL((gemm_bf16_big_kernel<0, bf16_t, true>), gridb, dim3(GG_THREADS), 0, st, a);
-        } else {
-            if (f32out) hipLaunchKernelGGL((gemm_bf16_big_kernel<2, float, true>), gridb, dim3(GG_THREADS), 0, st, a);
-            else hipLaunchKernelGGL((gemm_bf16_big_kernel<2, bf16_t, true>), gridb, dim3(GG_THREADS), 0, st, a);
-        }
+        if (layout == 0 && f32out) hipLaunchKernelGGL((gemm_bf16_big_kernel<0, float, true>), gridb, dim3(GG_THREADS), 0, st, a);
+        else if (layout == 0) hipLaunchKernelGGL((gemm_bf16_big_kernel<0, bf16_t, true>), gridb, dim3(GG_THREADS), 0, st, a);
+        else if (f32out) hipLaunchKernelGGL((gemm_bf16_big_kernel<2, float, true>), gridb, dim3(GG_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((gemm_bf16_big_kernel<2, bf16_t, true>), gridb, dim3(GG_THREADS), 0, st, a);
         SEGF_CHECK_LAUNCH();
-        goto reduce3;
-    }
-    {
-    dim3 grid((unsigned)cdiv64(a.N, GB_BN), (unsigned)cdiv64(a.M, GB_BM), (unsigned)split_k);
-    if (grid.y > 65535u) return SEGF_ERR_SHAPE;
-    if (layout == 0) {
-        if (f32out) hipLaunchKernelGGL((gemm_bf16_kernel<0, float, true, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((gemm_bf16_kernel<0, bf16_t, true, true>), grid, dim3(256), 0, st, a);
     } else {
-        if (f32out) hipLaunchKernelGGL((gemm_bf16_kernel<2, float, true, true>), grid, dim3(256), 0, st, a);
+        dim3 grid((unsigned)cdiv64(a.N, GB_BN), (unsigned)cdiv64(a.M, GB_BM), (unsigned)split_k);
+        if (grid.y > 65535u) return SEGF_ERR_SHAPE;
+        if (layout == 0 && f32out) hipLaunchKernelGGL((gemm_bf16_kernel<0, float, true, true>), grid, dim3(256), 0, st, a);
+        else if (layout == 0) hipLaunchKernelGGL((gemm_bf16_kernel<0, bf16_t, true, true>), grid, dim3(256), 0, st, a);
+        else if (f32out) hipLaunchKernelGGL((gemm_bf16_kernel<2, float, true, true>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((gemm_bf16_kernel<2, bf16_t, true, true>), grid, dim3(256), 0, st, a);
-    }
-    SEGF_CHECK_LAUNCH();
-    }
-reduce3:
-    if (a.ws) {
-        if (y_dt == SEGF_F32) splitk_reduce_launch<float>(st, ws, split_k, a.M, a.N, (float*)y, ldy, nullptr, nullptr, 0);
-        else splitk_reduce_launch<bf16_t>(st, ws, split_k, a.M, a.N, (bf16_t*)y, ldy, nullptr, nullptr, 0);
         SEGF_CHECK_LAUNCH();
     }
-    return 0;
+    return gemm_reduce_tail(st, a, y_dt, split_k, 0);
 }
 
 
@@ -2767,7 +2820,7 @@ reduce3:
 extern "C" int segf_conv3x3_fp8_supported(int mode, int B, int H, int W, int Cin, int Cout) {
     if (POL(no_fp8_conv) || mode < 0 || mode > 1 || B <= 0 || H <= 0 || W <= 0 || Cin % 16 || Cout % 16) return 0;
     const int64_t P = (int64_t)B * H * W, N = mode == 0 ? Cout : Cin, K = 9 * (int64_t)(mode == 0 ? Cin : Cout) / 2;
-    return gemm_use_big(0, P, N, K) ? 1 : 0;
+    return gemm_tile_shape(0, P, N, K) == TileShape::Big ? 1 : 0;
 }
 extern "C" int segf_conv3x3_fp8(int mode, int B, int H, int W, int Cin, int Cout, const void* xq, int64_t ldx, const float* sx,
                                 const void* wq, int64_t ldw, const float* sw, void* y, int64_t ldy, void* stream) {
@@ -2778,15 +2831,13 @@ extern "C" int segf_conv3x3_fp8(int mode, int B, int H, int W, int Cin, int Cout
     const int64_t P = (int64_t)B * H * W;
     const int Kc = mode == 0 ? Cin : Cout;                      // channels of the gathered operand
     GemmArgs a;
-    a.bias = nullptr; a.residual = nullptr; a.rscale = nullptr; a.ldr = 0; a.rpg = 1;
-    a.a_vec = 1; a.b_vec = 1; a.r_vec = 0; a.use_tr = 1; a.fast = 0; a.xcd_slabs = 0;
+    a.a_vec = 1; a.b_vec = 1; a.use_tr = 1;
     a.cH = H; a.cW = W; a.csign = mode == 1 ? -1 : 1;
-    a.colsum = nullptr; a.colsum_ws = nullptr; a.pro_scale = nullptr; a.pro_shift = nullptr; a.pro_rpg = 1; a.pro_ld = 0; a.pro_act = 0;
     a.f8_sa = sx; a.f8_sb = sw;
     a.M = P; a.N = mode == 0 ? Cout : Cin; a.K = 9 * (int64_t)Kc / 2;          // 2-byte units
     a.A = xq; a.lda = ldx / 2; a.B = wq; a.ldb = ldw / 2; a.cC = Kc / 2;
     a.C = y; a.ldc = ldy;
-    a.kchunk = cdiv64(a.K, GB_BK) * GB_BK; a.ws = nullptr;
+    a.kchunk = cdiv64(a.K, GB_BK) * GB_BK;
     a.c_vec = 1; a.c_vec16 = 1;
     if (gemm8_supported(0, 1, a.M, a.N, a.K, a.kchunk, a.cC))
         return gemm8_launch(0, 1, mode == 0 ? 1 : 2, a.M, a.N, a.K, a.kchunk, 1, a.A, a.lda, a.B, a.ldb, y, ldy, H, W, a.cC, a.csign, sx, sw,
@@ -2802,30 +2853,31 @@ extern "C" int segf_conv3x3_fp8(int mode, int B, int H, int W, int Cin, int Cout
 // mode 2 on fp8 operands: dW[co][tap*Cin+ci] = sg * sx * sum_pix gq[pix][co] xq[pix+off(tap)][ci]   (gq e5m2, xq e4m3: the tensors the
 // forward and the data gradient already quantised; one byte per element, row strides in bytes).  fp32 out [Cout][9*Cin]; split over K
 // (pixels) into fp32 slabs: ws >= split_k * Cout * 9 * Cin floats when split_k > 1 (segf_gemm_pick_splitk(Cout, 9 * Cin, B*H*W)).
+// both fp8 weight gradients: dW [M x N] over K tokens on the eight-phase tile (kind 3), slices of whole 128-token steps, one reduce pass
+static int fp8_wgrad_run(int conv, int64_t M, int64_t N, int64_t K, const void* gq, int64_t ldg, const float* sg, const void* xq, int64_t ldx,
+                         const float* sx, float* dw, int64_t lddw, int H, int W, int Cin, int split_k, float* ws, hipStream_t st) {
+    if (split_k < 1) split_k = 1;
+    if (split_k > 1 && !ws) return SEGF_ERR_WORKSPACE;
+    const int64_t kchunk = cdiv64(cdiv64(K, split_k), 128) * 128;
+    split_k = (int)cdiv64(K, kchunk);
+    if (!gemm8_supported(3, conv, M, N, K, kchunk, Cin)) return SEGF_ERR_SHAPE;
+    const int rc = gemm8_launch(3, conv, 2, M, N, K, kchunk, split_k, gq, ldg, xq, ldx, dw, lddw, H, W, Cin, 1, sg, sx, nullptr, nullptr, 0, nullptr,
+                                1, ws, st);
+    if (rc || split_k == 1) return rc;
+    splitk_reduce_launch<float>(st, ws, split_k, M, N, dw, lddw, nullptr, nullptr, 0);
+    SEGF_CHECK_LAUNCH();
+    return 0;
+}
 extern "C" int segf_conv3x3_fp8_wgrad_supported(int B, int H, int W, int Cin, int Cout) {
     if (POL(no_fp8_conv) || POL(no_fp8_wgrad) || B <= 0 || H <= 0 || W <= 0) return 0;
     const int64_t P = (int64_t)B * H * W, M = Cout, N = 9 * (int64_t)Cin;
-    if (!gemm_use_big(2, M, N, P)) return 0;
+    if (gemm_tile_shape(2, M, N, P) != TileShape::Big) return 0;
     return gemm8_supported(3, 1, M, N, P, 512, Cin);
 }
 extern "C" int segf_conv3x3_fp8_wgrad(int B, int H, int W, int Cin, int Cout, const void* xq, int64_t ldx, const float* sx, const void* gq,
                                       int64_t ldg, const float* sg, float* dw, int64_t lddw, int split_k, float* ws, void* stream) {
     if (!segf_conv3x3_fp8_wgrad_supported(B, H, W, Cin, Cout) || !xq || !gq || !sx || !sg || !dw) return SEGF_ERR_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t P = (int64_t)B * H * W, M = Cout, N = 9 * (int64_t)Cin;
-    if (split_k < 1) split_k = 1;
-    if (split_k > 1 && !ws) return SEGF_ERR_WORKSPACE;
-    int64_t kchunk = cdiv64(cdiv64(P, split_k), 128) * 128;
-    split_k = (int)cdiv64(P, kchunk);
-    if (!gemm8_supported(3, 1, M, N, P, kchunk, Cin)) return SEGF_ERR_SHAPE;
-    const int rc = gemm8_launch(3, 1, 2, M, N, P, kchunk, split_k, gq, ldg, xq, ldx, dw, lddw, H, W, Cin, 1, sg, sx, nullptr, nullptr, 0, nullptr,
-                                1, ws, st);
-    if (rc) return rc;
-    if (split_k > 1) {
-        splitk_reduce_launch<float>(st, ws, split_k, M, N, dw, lddw, nullptr, nullptr, 0);
-        SEGF_CHECK_LAUNCH();
-    }
-    return 0;
+    return fp8_wgrad_run(1, Cout, 9 * (int64_t)Cin, (int64_t)B * H * W, gq, ldg, sg, xq, ldx, sx, dw, lddw, H, W, Cin, split_k, ws, (hipStream_t)stream);
 }
 
 // ---- nn.Linear products on fp8 operands, one dynamic scale per activation / gradient TENSOR (segf_quant_tensor_fp8) and one per weight
@@ -2866,18 +2918,5 @@ extern "C" int segf_linear_fp8_wgrad(int64_t N, int64_t K, int64_t T, const void
                                      int64_t ldx, const float* sx, float* dw, int64_t lddw, int split_k, float* ws, void* stream) {
     if (!segf_linear_fp8_supported(2, T, N, K)) return SEGF_ERR_SHAPE;
     if (!gq || !xq || !sg || !sx || !dw || ldg < N || ldx < K || lddw < K) return SEGF_ERR_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    if (split_k < 1) split_k = 1;
-    if (split_k > 1 && !ws) return SEGF_ERR_WORKSPACE;
-    int64_t kchunk = cdiv64(cdiv64(T, split_k), 128) * 128;
-    split_k = (int)cdiv64(T, kchunk);
-    if (!gemm8_supported(3, 0, N, K, T, kchunk, 0)) return SEGF_ERR_SHAPE;
-    const int rc = gemm8_launch(3, 0, 2, N, K, T, kchunk, split_k, gq, ldg, xq, ldx, dw, lddw, 0, 0, 0, 1, sg, sx, nullptr, nullptr, 0, nullptr,
-                                1, ws, st);
-    if (rc) return rc;
-    if (split_k > 1) {
-        splitk_reduce_launch<float>(st, ws, split_k, N, K, dw, lddw, nullptr, nullptr, 0);
-        SEGF_CHECK_LAUNCH();
-    }
-    return 0;
+    return fp8_wgrad_run(0, N, K, T, gq, ldg, sg, xq, ldx, sx, dw, lddw, 0, 0, 0, split_k, ws, (hipStream_t)stream);
 }

@@ -102,8 +102,9 @@ def unique(calls):
     return out
 
 
-def replay(entry):
-    """Dry run of one recorded call: the kernel names the library's dispatch picks NOW for these arguments."""
+def replay_rc(entry, low=(0, 0, 0, 0, 0)):
+    """Dry run of one recorded call -> (return code, kernel names).  `low` = the low address bits of a grouped call's placeholder
+    pointers (dy, x, dw, db, ws): the other entry points carry theirs in the arguments ('p8')."""
     lib = hip.lib()
     name, args = entry['fn'], entry['args']
     with hip.trace(dry_run=True) as t:
@@ -113,11 +114,17 @@ def replay(entry):
             for k, (M, N, K, lddy, ldx, lddw, split_k, shared) in enumerate(desc):
                 it = arr[k]
                 it.M, it.N, it.K, it.lddy, it.ldx, it.lddw, it.split_k, it.shared_split = M, N, K, lddy, ldx, lddw, split_k, shared
-                it.dy, it.x, it.dw, it.db, it.ws = (_PLACEHOLDER + 0x1000 * (5 * k + j) for j in range(5))
+                it.dy, it.x, it.dw, it.db, it.ws = (_PLACEHOLDER + 0x1000 * (5 * k + j) + low[j] for j in range(5))
             rc = lib.segf_gemm_dw_db_grouped(dt, len(desc), C.cast(arr, C.c_void_p), None)
         else:
             argtypes = hip._DECLS[name][1]
             rc = getattr(lib, name)(*[_dec(a, v) for a, v in zip(argtypes, args)])
+    return rc, t.kernels
+
+
+def replay(entry):
+    """Dry run of one recorded call: the kernel names the library's dispatch picks NOW for these arguments."""
+    rc, kernels = replay_rc(entry)
     if rc != 0:
-        raise RuntimeError(f'{name}{tuple(args)} returned {rc} in a dry run')
-    return t.kernels
+        raise RuntimeError(f"{entry['fn']}{tuple(entry['args'])} returned {rc} in a dry run")
+    return kernels

@@ -501,6 +501,30 @@ def test_dispatch_of_baseline_shapes(golden_dir):
     assert not moved, moved[:5]
 
 
+def test_gemm_dispatch_sweep(golden_dir):
+    """csrc/gemm.hip's host dispatch beyond the BASELINE arguments: the rows of dispatch_table.json that its nine entry points serve,
+    replayed as dry runs under one perturbation at a time (each GEMM / implicit-GEMM policy switch flipped, misaligned operands, odd
+    leading dimensions, other slice counts, reshuffled groups), and the host queries that choose slice counts and size workspaces --
+    return codes and kernel lists as recorded in tests/golden/gemm_dispatch_sweep.json by tools/make_gemm_dispatch_sweep.py."""
+    import json
+    sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    import make_gemm_dispatch_sweep as tool
+    got = tool.generate()
+    with open(os.path.join(golden_dir, 'gemm_dispatch_sweep.json')) as fh:
+        text = fh.read()
+    want = json.loads(text)
+    assert got['n_rows'] > 700 and got['n_results'] > 30000 and got['n_query_results'] > 100000
+    assert got['rows_sha256'] == want['rows_sha256'], 'dispatch_table.json changed: regenerate the sweep'
+    ex_want, ex_got = tool.explain(want), tool.explain(got)
+    assert set(ex_got) == set(ex_want)
+    moved = [(name, i, ex_want[name].get(i), ex_got[name].get(i)) for name in ex_want for i in sorted(set(ex_want[name]) | set(ex_got[name]))
+             if ex_want[name].get(i) != ex_got[name].get(i)]
+    assert not moved, (len(moved), moved[:5])
+    assert got['queries']['base'] == want['queries']['base']
+    assert got['queries'] == want['queries'], [k for k, v in want['queries']['perturbed'].items() if v != got['queries']['perturbed'].get(k)]
+    assert tool.dumps(got) == text
+
+
 def test_bench_default_batches_resolve():
     """bench.py / tools/bench_legs.py: a configuration without --batch runs at bench.DEFAULT_BATCH (r05: a misplaced comment once made the
     legs' default the whole table, and the cfg3 / cfg4 / cfg5 legs of the default line failed on the GPU box only)."""
