@@ -243,7 +243,9 @@ int segf_colreduce_finalize_grouped(int n, const SegfFinalizeItem* items, void* 
 
 /* ---- BatchNorm2d (train: batch statistics) + ReLU/ReLU6 + Dropout2d, NHWC rows -------------------
  * ConvModule of heads/segformer.py:21-29, layers/conv_module.py:4-9, mobilenetv2.py:5-11.
- * stats: mean/var(biased) over rows; running stats updated with momentum and unbiased var.         */
+ * stats: mean/var(biased) over rows; running stats updated with momentum and unbiased var.
+ * Accuracy: the variance is E[x^2] - mean^2 from fp32 sums of x and x^2 (combined in double), so it is as accurate as those sums allow
+ * and its relative error grows as (mean / sigma)^2 (tests/test_norm_float64.py pins this).                    */
 int64_t segf_bn_ws(int64_t rows, int C);
 int segf_bn_stats(int dt, int64_t rows, int C, const void* x, float* mean, float* rstd,
                   float* running_mean, float* running_var, float momentum, float eps, float* ws, void* stream);
@@ -451,6 +453,8 @@ int64_t segf_fuse_map_248_ws(int B, int H, int W, int C);
 int segf_fuse_map_248(int B, int H, int W, int C, int C1, const void* x1, int64_t ldx1, const void* g1, int64_t ldg,
                       const void* t2, int64_t ld2, const void* t3, int64_t ld3, const void* t4, int64_t ld4,
                       void* out, int64_t ldo, float* sums, float* ws, void* stream);
+/* (the accuracy of segf_bn_stats: the variance is as accurate as the fp32 sums of x and x^2 it is given allow, so its relative error
+ * grows as (mean / sigma)^2) */
 int segf_bn_stats_from_sums(const float* sums, int64_t rows, int C, float* mean, float* rstd, float* running_mean,
                             float* running_var, float momentum, float eps, void* stream);
 /* Nearest-neighbour resize on dense NHWC (F.interpolate mode='nearest': the top-down step of FPNHead, heads/fpn.py:31,35).

@@ -362,6 +362,8 @@ extern "C" int segf_colreduce_finalize_grouped(int n, const SegfFinalizeItem* it
 }
 
 // ---- BatchNorm on NHWC rows ---------------------------------------------------------------------------------
+// Accuracy of the statistics: the variance is E[x^2] - mean^2 from fp32 sums of x and x^2 (combined in double), so it is as accurate as
+// those sums allow and its relative error grows as (mean / sigma)^2 (tests/test_norm_float64.py pins this).
 template <typename T> struct BnStatF {
     const T* x; int C; bool vec;
     struct Col {};

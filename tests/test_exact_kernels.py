@@ -16,8 +16,9 @@ of the tensor; a dropped K element, a K slab counted twice, a truncating store o
 Beside the table: products whose feature sizes N and K are one more and one less than a tile multiple (test_exact_feature_ragged_gemm),
 and the depthwise 7 x 7 / 3 x 3 convolutions, the bilinear resize by 2 / 4 / 8 and the column sum (test_exact_spatial_kernels).
 
-Not covered by this module (they keep their tolerance tests): kernels with a division or a transcendental (norms, GELU, softmax-CE, fp8
-quantisation), the bilinear backward / fused forms (bilinear_bwd, bilinear_bwd_248, upsample_add, fuse_map_248) and the pure data movers
+Not covered by this module: kernels with a division or a transcendental.  Of those the norms and the column reductions (LayerNorm,
+BatchNorm, GRN, colsum) are checked against float64 in tests/test_norm_float64.py; GELU, softmax-CE and fp8 quantisation keep their
+tolerance tests, as do the bilinear backward / fused forms (bilinear_bwd, bilinear_bwd_248, upsample_add, fuse_map_248) and the pure data movers
 (im2col, col2im, permute021, nearest_up, cast2d), for which tests/exact_inputs.py has no reference yet.
 """
 import ctypes as C

@@ -3,7 +3,9 @@ against a plain PyTorch fp32 CPU statement of the same op.  fp32 storage must ma
 storage to 3 % of the largest element of the tensor (more on gradients: `_close`).  That bar catches a kernel that is wrong
 by a standard deviation, NOT one that is wrong by a rounding, a dropped K element or a K slab counted twice: the bit-exact
 checks of the matrix and attention kernels (rounding of the stores, fp32 accumulation, every term counted once) are in
-tests/test_exact_kernels.py."""
+tests/test_exact_kernels.py, and the norms and column reductions (LayerNorm, BatchNorm, GRN, colsum: a misplaced eps, n against n - 1, a
+dropped row, the paths that only large or ragged shapes reach) are held to the fp32 error of a float64 reference in
+tests/test_norm_float64.py."""
 import math
 import os
 
