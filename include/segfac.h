@@ -485,7 +485,21 @@ int segf_ce_dice_fwd(int dt, int B, int C, int h, int w, int H, int W, const voi
                      float* stats, float* loss, float* pix_lse, void* stream);
 /* dlogits: NHWC [B][h][w][ldd] of dtype dt = grad_out[0] * d loss / d logits (the LOW-resolution head output; the
  * transposed bilinear resize is applied inside; columns [C, ldd) are zeroed).  ws: segf_ce_dice_bwd_ws floats
- * (0 on the fused power-of-two path; the generic path stages the full-resolution gradient there).        */
+ * (0 on the fused power-of-two path; the generic path stages the full-resolution gradient there).
+ * Accuracy contract (tests/test_loss_float64.py holds every path to it, against float64):
+ *   - a pixel with the ignore index has no term at all: a batch without a valid pixel gives loss = {NaN, NaN, 0} (0 / 0 as
+ *     F.cross_entropy; every Dice term is 1) and a gradient of exact zeros on every path, as autograd does;
+ *   - bf16, ratio 4: exponentials and the per-pixel coefficients go * (wce - <G, p>) * tap weight are bf16 operands of the scatter,
+ *     so a gradient element is accurate to 2^-9 of the sum of the absolute values of its parts, not of its own size.  At the label
+ *     class of a confident pixel go * wce * p_t passes through bf16 and meets -go * wce in fp32: the error there is relative to
+ *     go * wce, not to p_t - 1;
+ *   - bf16, ratios that are no power of two: the staged full-resolution gradient is bf16, each pixel's d loss / d z is rounded
+ *     (2^-8 relative) before the transposed resize adds them;
+ *   - ratio-4 matrix-pipe kernels, both types: log2(e) rides in the interpolation operand, so a logit in the exp2 domain is rounded
+ *     relative to its own size: the CE sum carries 2 * 2^-24 * (|log-sum-exp| + |z_t|) per pixel (logits near +-200: 1e-5 of a
+ *     pixel's term), the probabilities and the gradient do not (the stabiliser is subtracted in the accumulator);
+ *   - exponentials below 2^-126 of the largest logit of a cell's four taps are zero (the retry flag is raised only when a
+ *     pixel's whole sum falls below 1e-30).                                                                  */
 int64_t segf_ce_dice_bwd_ws(int dt, int B, int C, int h, int w, int H, int W);
 int segf_ce_dice_bwd(int dt, int B, int C, int h, int w, int H, int W, const void* logits, int64_t ldl,
                      const int64_t* target, int64_t ignore_index, const float* class_weight, int dice,

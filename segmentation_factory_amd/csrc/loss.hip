@@ -721,7 +721,7 @@ __global__ void __launch_bounds__(LS_THREADS, 4) ce_dice_bwd_cells8_kernel(const
                         if (t >= 0 && under) slow |= 1u;
                         const float okf = (t >= 0 && !under) ? 1.f : 0.f;
                         const float inv = okf * __builtin_amdgcn_rcpf(fmaxf(tot[i], 1e-30f));
-                        const float wce = okf * (cw ? cw[tt] : 1.f) * invW;
+                        const float wce = okf != 0.f ? (cw ? cw[tt] : 1.f) * invW : 0.f;   // no CE term, also where invW = 1 / 0 (no valid pixel in the batch)
                         const float c1 = go * inv, k = wce - dtot[i] * inv, c2 = go * wce;
 #pragma unroll
                         for (int s = 0; s < NS; ++s) {
@@ -1012,7 +1012,7 @@ __global__ void __launch_bounds__(LS_THREADS) ce_dice_bwd_mfma4_kernel(const T* 
             slow |= under;
             const float okf = (valid && !under) ? 1.f : 0.f;
             const float inv = okf * __builtin_amdgcn_rcpf(fmaxf(tot, 1e-30f));
-            const float wce = okf * (cw ? cw[m.tt] : 1.f) * invW;
+            const float wce = okf != 0.f ? (cw ? cw[m.tt] : 1.f) * invW : 0.f;   // no CE term, also where invW = 1 / 0 (no valid pixel in the batch)
             const float et = __builtin_amdgcn_exp2f(zt), git = gIs[m.tt];
             const float c1 = go * inv;
             const float k = wce - (dpm + git * et) * inv;                  // wce - <G, p>

@@ -355,7 +355,7 @@ __global__ void __launch_bounds__(LS_THREADS, BAND_OCC) ce_dice_bwd_band_kernel(
                 slow |= under;
                 const float okf = (valid && !under) ? 1.f : 0.f;
                 const float inv = LSE ? okf : okf * __builtin_amdgcn_rcpf(fmaxf(tot, 1e-30f));
-                const float wce = okf * gw.y * invW;
+                const float wce = okf != 0.f ? gw.y * invW : 0.f;              // no CE term, also where invW = 1 / 0 (no valid pixel in the batch)
                 const float et = __builtin_amdgcn_exp2f(zt), git = gw.x;
                 const float c1 = go * inv;
                 const float kk = wce - (dpm + git * et) * inv;                 // wce - <G, p>
