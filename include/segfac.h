@@ -506,6 +506,50 @@ int segf_ce_dice_bwd(int dt, int B, int C, int h, int w, int H, int W, const voi
                      const float* stats, const float* grad_out, void* dlogits, int64_t ldd, float* ws,
                      const float* pix_lse, void* stream);
 
+/* ---- per-pixel losses on the fused low-resolution path: OhemCrossEntropy and FocalLoss (util/losses.py:9-66) applied to
+ * F.interpolate(logits, (H, W), bilinear, align_corners=False) (build_models.py:65) without forming full-resolution logits or
+ * gradients.  Arguments as segf_ce_dice_fwd; C <= 192, B*H*W < 2^31, bf16 and fp32 storage; anything else returns
+ * SEGF_ERR_SHAPE before any launch (segf_pixel_loss_supported answers 0).
+ * Per pixel ce = w[t] * (logsumexp(z) - z_t) for t != ignore_index, +0.0 for t == ignore_index (w = 1 when class_weight is
+ * NULL).  Interpolation, log-sum-exp and ce are fp32 computed from the stored values WHATEVER the storage type, so a bf16 and an
+ * fp32 run of the same stored numbers select the same pixels.  ce_map: fp32 [B][H][W], every value >= +0 with the sign bit clear.
+ * A label that is neither ignore_index nor in [0, C) is treated as segf_ce_dice_fwd treats it: skipped (ce = 0, not counted as
+ * valid, no gradient) and flagged in the state.
+ * mode 0, OHEM (p0 = theta = float32(-log(thresh)), 0 < thresh < 1; p1, size_average unused):
+ *   n_valid = #(t != ignore), n_min = n_valid / 16, n_hard = #(ce > theta) over all B*H*W pixels, compared in fp32.
+ *   n_hard >= n_min: selection {ce > theta}, n_sel = n_hard, loss = mean of the selection.
+ *   otherwise (used_topk): the n_min largest of ALL pixels; kappa = the n_min-th largest value, n_gt = #(ce > kappa),
+ *   n_eq = #(ce == kappa), n_sel = n_min, loss = (sum_{ce > kappa} ce + (n_min - n_gt) kappa) / n_min.
+ *   n_sel == 0 (all labels ignored, or fewer than 16 valid pixels and none hard): loss = NaN, gradient exact zeros, as the reference.
+ *   Gradient coefficient of a pixel: grad_out / n_sel above the decision value (theta or kappa), 0 below.  Ties at kappa: torch.topk
+ *   keeps arbitrary members; here EVERY pixel with ce == kappa gets grad_out (n_min - n_gt) / (n_eq n_min).  The loss is the
+ *   reference's; the gradient is a deterministic member of the reference's possible ones.  An ignored pixel never has a gradient.
+ *   The branch is decided on the device (no host synchronisation); the launch sequence is the same on every call, so a captured
+ *   graph replays whichever branch the data takes.
+ * mode 1, focal (p0 = alpha, p1 = gamma >= 0; no class weights in the reference class, class_weight is honoured if given):
+ *   pt = exp(-ce), f = alpha (1 - pt)^gamma ce, loss = sum f / (B H W) (ignored pixels count in the divisor, as .mean() does) or
+ *   sum f when size_average == 0.  Coefficient: grad_out alpha [(1 - pt)^gamma + gamma (1 - pt)^(gamma-1) pt ce] / N; the second
+ *   term is 0 when gamma == 0 or ce == 0.
+ * state: segf_pixel_loss_state_words(B) 32-bit words; the first eight are readable by the caller:
+ *   int32 {n_valid, n_min, n_hard, n_gt, n_eq, used_topk}, fp32 kappa (the decision value: theta in the threshold branch), int32
+ *   bad_label_flag; the rest is scratch (histograms, partial sums).  In mode 1 only n_valid and the flag are meaningful.
+ * loss: fp32 [1].  No floating-point atomics: float sums are per-workgroup partials added in float64 in a fixed order, counts are
+ * integer atomics; two runs on the same inputs give the same bits in loss, ce_map, state and dlogits.
+ * Backward: takes the forward's ce_map and state (the side of the decision value is read from the saved map, not recomputed);
+ * dlogits NHWC [B][h][w][ldd] of dtype dt = sum over pixels of coef w[t] (softmax(z) - onehot_t) through the transposed resize,
+ * columns [C, ldd) zeroed (ldd <= 64 ceil(C / 64)).  ws: segf_pixel_loss_bwd_ws floats (0 when H/h == W/w is a power of two
+ * <= 8; other ratios stage the full-resolution gradient there and use segf_bilinear_bwd).                              */
+int segf_pixel_loss_supported(int dt, int mode, int B, int C, int h, int w, int H, int W);
+int64_t segf_pixel_loss_state_words(int B);
+int64_t segf_pixel_loss_bwd_ws(int dt, int B, int C, int h, int w, int H, int W);
+int segf_pixel_loss_fwd(int dt, int mode, int B, int C, int h, int w, int H, int W, const void* logits, int64_t ldl,
+                        const int64_t* target, int64_t ignore_index, const float* class_weight, float p0, float p1,
+                        int size_average, float* ce_map, int32_t* state, float* loss, void* stream);
+int segf_pixel_loss_bwd(int dt, int mode, int B, int C, int h, int w, int H, int W, const void* logits, int64_t ldl,
+                        const int64_t* target, int64_t ignore_index, const float* class_weight, float p0, float p1,
+                        int size_average, const float* ce_map, const int32_t* state, const float* grad_out, void* dlogits,
+                        int64_t ldd, float* ws, void* stream);
+
 /* test hook: out[16] = column sums of in[64][16] through the loss kernels' transposing wave reduction */
 int segf_debug_wave_reduce16(const float* in, float* out, void* stream);
 

@@ -10,6 +10,7 @@ is missing.
 from .build_models import SegmentationModel, head_dict, backbone_registry, register_backbone, register_head  # noqa: F401
 from .engine import criterion, criterion_lowres, evaluate, train_one_epoch  # noqa: F401
 from .metrics import Metrics  # noqa: F401
+from .losses import CrossEntropy, OhemCrossEntropy, FocalLoss, get_loss  # noqa: F401   (util/losses.py's classes)
 from .inference import SemSeg  # noqa: F401   (estimate_model.py's SemSeg for tensors)
 
 __version__ = '0.1.0'

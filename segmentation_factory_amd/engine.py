@@ -121,6 +121,23 @@ def _fall_back_to_eager(core, model, optimizer, device, err):
     return model
 
 
+def _named_loss(args):
+    """The loss class `args.loss` names (losses.py; util/losses.py of the reference), or None for the engine's own criterion
+    (`loss` absent, None or 'ce_dice').  Two-class runs get the weights engine.py:28-32 gives its criterion; FocalLoss takes none."""
+    name = getattr(args, 'loss', None)
+    if name is None or name == 'ce_dice':
+        return None
+    from . import losses
+    weight = [1.0, 2.0] if args.nb_classes == 2 else None
+    if name == 'CrossEntropy':
+        return losses.CrossEntropy(args.ignore_index, weight)
+    if name == 'OhemCrossEntropy':
+        return losses.OhemCrossEntropy(args.ignore_index, weight, thresh=getattr(args, 'ohem_thresh', 0.7))
+    if name == 'FocalLoss':
+        return losses.FocalLoss(getattr(args, 'focal_alpha', 1.0), getattr(args, 'focal_gamma', 0.0), True, args.ignore_index)
+    raise ValueError(f"args.loss: expected ce_dice, CrossEntropy, OhemCrossEntropy or FocalLoss, got {name!r}")
+
+
 def train_one_epoch(model, optimizer, dataloader, epoch, device, print_freq, clip_grad, clip_mode, loss_scaler,
                     writer=None, args=None):
     model.train()
@@ -131,6 +148,11 @@ def train_one_epoch(model, optimizer, dataloader, epoch, device, print_freq, cli
     loss_weight = torch.as_tensor([1.0, 2.0], device=device) if args.nb_classes == 2 else None   # engine.py:28-32
     core = model.module if hasattr(model, 'module') else model
     fused = hasattr(core, 'forward_lowres')
+    # built once per model and configuration: the captured step of a later epoch keeps calling the object it was captured with
+    loss_key = tuple(getattr(args, k, None) for k in ('loss', 'ohem_thresh', 'focal_alpha', 'focal_gamma', 'nb_classes', 'ignore_index'))
+    if getattr(core, '_named_loss', (None, None))[0] != loss_key:
+        core._named_loss = (loss_key, _named_loss(args))
+    named_loss = core._named_loss[1]
     use_graph = _graph_step_wanted(args, model, core, optimizer, loss_scaler, device)
     if getattr(core, '_ddp_fallback', None) is not None:
         model = core._ddp_fallback      # an earlier capture failed under several ranks: DistributedDataParallel carries the exchange
@@ -143,10 +165,12 @@ def train_one_epoch(model, optimizer, dataloader, epoch, device, print_freq, cli
             # the whole step (zero_grad, forward, criterion, backward, gradient gather) replayed as one hipGraph, followed by
             # the RCCL all-reduce of the flat gradient buffer and the fused AGC/AdamW kernel (graph.py)
             from .graph import GraphedTrainStep
-            key = (tuple(img.shape), tuple(lbl.shape), clip_grad, clip_mode)
+            key = (tuple(img.shape), tuple(lbl.shape), clip_grad, clip_mode) + ((loss_key,) if named_loss is not None else ())
             gs = getattr(core, '_graphed_step', None)
             if gs is None or gs.key != key:
                 def loss_fn(m, x, y, _lw=loss_weight, _hw=tuple(img.shape[2:])):
+                    if named_loss is not None:
+                        return named_loss(m.forward_lowres(x), y)
                     return criterion_lowres(m.forward_lowres(x), y, _hw, _lw, num_classes=args.nb_classes, dice=args.dice,
                                             ignore_index=args.ignore_index)
                 core._graphed_step = gs = None
@@ -185,8 +209,13 @@ def train_one_epoch(model, optimizer, dataloader, epoch, device, print_freq, cli
                 lo = TokenMap(data, b_, h_, w_)
             else:
                 lo = core.forward_lowres(img)
-            loss = criterion_lowres(lo, lbl, img.shape[2:], loss_weight, num_classes=args.nb_classes, dice=args.dice,
-                                    ignore_index=args.ignore_index)
+            if named_loss is not None:
+                loss = named_loss(lo, lbl)
+            else:
+                loss = criterion_lowres(lo, lbl, img.shape[2:], loss_weight, num_classes=args.nb_classes, dice=args.dice,
+                                        ignore_index=args.ignore_index)
+        elif named_loss is not None:
+            loss = named_loss(model(img), lbl)
         else:
             loss = criterion(model(img), lbl, loss_weight, num_classes=args.nb_classes, dice=args.dice,
                              ignore_index=args.ignore_index)

@@ -1796,6 +1796,72 @@ def upsample_ce_dice(logits, target, geom, ignore_index=255, class_weight=None, 
     return UpsampleCEDiceFn.apply(logits, target, tuple(geom), int(ignore_index), class_weight, bool(dice))
 
 
+class UpsamplePixelLossFn(Function):
+    """OhemCrossEntropy / FocalLoss of util/losses.py:9-66 on F.interpolate(logits, size) (build_models.py:65) without the
+    full-resolution logits: the forward leaves the fp32 per-pixel CE map and the device-side selection state, the backward
+    reads both (include/segfac.h, segf_pixel_loss_*)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, geom, mode, params, ignore_index, class_weight):
+        B, Cc, h, w, H, W = geom
+        logits = _rowmajor(logits)
+        if not target.is_cuda or target.device != logits.device:
+            raise RuntimeError('pixel loss: target must be a device tensor on the logits\' device (no CPU fallback)')
+        if target.dtype != torch.int64:
+            raise RuntimeError(f'pixel loss: expected an int64 (Long) target, got {target.dtype}')
+        if target.numel() != B * H * W:
+            raise RuntimeError(f'pixel loss: target has {target.numel()} elements, expected B*H*W = {B * H * W}')
+        if logits.shape[0] != B * h * w or logits.shape[1] < Cc:
+            raise RuntimeError(f'pixel loss: logits {tuple(logits.shape)} do not match geometry {geom}')
+        if not hip.pixel_loss_supported(logits.dtype, mode, B, Cc, h, w, H, W):
+            raise RuntimeError(f'pixel loss: geometry {geom} / {logits.dtype} has no kernel (C <= 192, B*H*W < 2^31)')
+        target = target.contiguous()
+        p0, p1, size_average = params
+        loss, ce_map, state = hip.pixel_loss_fwd(logits, B, Cc, h, w, H, W, target, ignore_index, class_weight, mode, p0, p1,
+                                                 size_average)
+        ctx.save_for_backward(logits, target, class_weight, ce_map, state)
+        ctx.meta = (geom, mode, params, ignore_index)
+        info = state[:8]
+        ctx.mark_non_differentiable(ce_map, info)
+        ctx.set_materialize_grads(False)
+        return loss[0], ce_map, info
+
+    @staticmethod
+    def backward(ctx, gloss, _gmap, _ginfo):
+        logits, target, cw, ce_map, state = ctx.saved_tensors
+        (B, Cc, h, w, H, W), mode, (p0, p1, size_average), ignore_index = ctx.meta
+        if gloss is None:
+            return None, None, None, None, None, None, None
+        go = gloss.reshape(1).to(torch.float32).contiguous()
+        dl = hip.pixel_loss_bwd(logits, B, Cc, h, w, H, W, target, ignore_index, cw, mode, p0, p1, size_average, ce_map, state,
+                                go)[:, :Cc]
+        return dl, None, None, None, None, None, None
+
+
+PIXEL_INFO_FIELDS = ('n_valid', 'n_min', 'n_hard', 'n_gt', 'n_eq', 'used_topk', 'kappa', 'bad_label')
+
+
+def upsample_pixel_loss(logits, target, geom, mode, params, ignore_index=255, class_weight=None):
+    """mode 'ohem', params (theta,): OhemCrossEntropy with theta = float32(-log(thresh)); mode 'focal', params (alpha, gamma,
+    size_average): FocalLoss.  Returns (loss, ce_map [B, H, W] fp32, info); info is the int32[8] head of the device state in the
+    order of PIXEL_INFO_FIELDS (kappa: fp32 bits, see pixel_loss_info).  ce_map and info are non-differentiable."""
+    if mode == 'ohem':
+        code, prm = hip.PIXEL_OHEM, (float(params[0]), 0.0, 1)
+    elif mode == 'focal':
+        code, prm = hip.PIXEL_FOCAL, (float(params[0]), float(params[1]), 1 if params[2] else 0)
+    else:
+        raise ValueError(f"upsample_pixel_loss: mode must be 'ohem' or 'focal', got {mode!r}")
+    return UpsamplePixelLossFn.apply(logits, target, tuple(geom), code, prm, int(ignore_index), class_weight)
+
+
+def pixel_loss_info(info):
+    """Host dict of upsample_pixel_loss's info (one synchronising copy): the integers plus kappa as a Python float."""
+    host = info.detach().cpu()
+    out = dict(zip(PIXEL_INFO_FIELDS, host.tolist()))
+    out['kappa'] = host[6:7].view(torch.float32).item()
+    return out
+
+
 class UpsampleToNCHWFn(Function):
     """F.interpolate(head_out, size=input, bilinear, align_corners=False) -> fp32 NCHW logits
     (build_models.py:65), for callers that want the reference's materialised tensor."""

@@ -1327,6 +1327,42 @@ def ce_dice_bwd(logits, B, Cc, h, w, H, W, target, ignore_index, class_weight, d
     return dlow
 
 
+PIXEL_OHEM, PIXEL_FOCAL = 0, 1          # mode of segf_pixel_loss_*
+
+
+def pixel_loss_supported(dtype, mode, B, Cc, h, w, H, W):
+    dt = {torch.float32: F32, torch.bfloat16: BF16}.get(dtype, -1)
+    return bool(lib().segf_pixel_loss_supported(dt, int(mode), B, Cc, h, w, H, W))
+
+
+def pixel_loss_fwd(logits, B, Cc, h, w, H, W, target, ignore_index, class_weight, mode, p0, p1, size_average):
+    """(loss[1], ce_map [B, H, W] fp32, state int32): state[:8] is the layout documented in include/segfac.h (kappa's fp32 bits at 6)."""
+    n = lib().segf_pixel_loss_state_words(B)
+    if n <= 0:
+        raise RuntimeError(f'segf_pixel_loss_state_words: unsupported batch size {B}')
+    state = torch.empty(n, dtype=torch.int32, device=logits.device)
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    ce_map = torch.empty((B, H, W), dtype=torch.float32, device=logits.device)
+    _chk(lib().segf_pixel_loss_fwd(dt_of(logits), int(mode), B, Cc, h, w, H, W, _ptr(logits), logits.stride(0), _ptr(target),
+                                   int(ignore_index), _ptr(class_weight), float(p0), float(p1), int(size_average), _ptr(ce_map),
+                                   _ptr(state), _ptr(loss), _stream()), 'segf_pixel_loss_fwd')
+    return loss, ce_map, state
+
+
+def pixel_loss_bwd(logits, B, Cc, h, w, H, W, target, ignore_index, class_weight, mode, p0, p1, size_average, ce_map, state,
+                   grad_out):
+    """d loss / d (low-res logits), same row stride as `logits` (pad columns zeroed), from pixel_loss_fwd's ce_map and state."""
+    ld = logits.stride(0)
+    dlow = torch.empty((B * h * w, ld), dtype=logits.dtype, device=logits.device)
+    dt = dt_of(logits)
+    nws = lib().segf_pixel_loss_bwd_ws(dt, B, Cc, h, w, H, W)
+    ws = _f32(nws, logits.device) if nws else None
+    _chk(lib().segf_pixel_loss_bwd(dt, int(mode), B, Cc, h, w, H, W, _ptr(logits), ld, _ptr(target), int(ignore_index),
+                                   _ptr(class_weight), float(p0), float(p1), int(size_average), _ptr(ce_map), _ptr(state),
+                                   _ptr(grad_out), _ptr(dlow), ld, _ptr(ws), _stream()), 'segf_pixel_loss_bwd')
+    return dlow
+
+
 def argmax_confmat(logits, B, Cc, h, w, H, W, target, ignore_label, mat, hist, flag, pred_out=None):
     _chk(lib().segf_argmax_confmat(dt_of(logits), B, Cc, h, w, H, W, _ptr(logits), logits.stride(0), _ptr(target),
                                    int(ignore_label), _ptr(mat), _ptr(hist), _ptr(flag), _ptr(pred_out), _stream()),

@@ -127,6 +127,13 @@ def get_args_parser():
     parser.add_argument('--eval-dtype', default='fp32', choices=['fp32', 'bf16'],
                         help="precision of evaluate()'s forward: fp32 as the reference (engine.py:86-88 switches autocast off), or the "
                              'bf16 production storage type')
+    parser.add_argument('--loss', default='ce_dice', choices=['ce_dice', 'CrossEntropy', 'OhemCrossEntropy', 'FocalLoss'],
+                        help="training loss: ce_dice = the reference engine's criterion (CE + Dice, see --dice), or one of the classes of "
+                             'util/losses.py on the fused low-resolution loss path (segmentation_factory_amd/losses.py; --dice is not consulted)')
+    parser.add_argument('--ohem-thresh', dest='ohem_thresh', default=0.7, type=float,
+                        help='--loss OhemCrossEntropy: pixels with a label probability below this are hard (0 < thresh < 1)')
+    parser.add_argument('--focal-alpha', dest='focal_alpha', default=1.0, type=float, help='--loss FocalLoss: alpha')
+    parser.add_argument('--focal-gamma', dest='focal_gamma', default=0.0, type=float, help="--loss FocalLoss: gamma (the class's default)")
     parser.add_argument('--grad-exchange', default='all_reduce', choices=['all_reduce', 'rs_ag'],
                         help='--hip-graph data parallelism: one all-reduce per gradient bucket, or in-place reduce-scatter + all-gather')
     parser.add_argument('--grad-payload', default='fp32', choices=['fp32', 'bf16'],
