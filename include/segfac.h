@@ -240,6 +240,29 @@ typedef struct SegfFinalizeItem { const float* partial; float* out; int64_t len;
  * (segf_dwconv3x3_bwd_blocks(dt, B, H, W, C) blocks in its ws) and land as out = dw[C][9] followed by db[C] (mit.py:62-71 backward). */
 int segf_layernorm_bwd_blocks(int64_t rows, int C);
 int segf_colreduce_finalize_grouped(int n, const SegfFinalizeItem* items, void* stream);
+/* The backward of `LayerNorm -> Linear` where the Linear is C -> N = 4 C wide, C = 32 or 64 (norm2 -> mlp.fc1 of a MiT block, mit.py:98,136-146)
+ * in ONE pass over the hidden-width gradient dh [rows][N] (csrc/norm.hip: ln_linear_bwd_kernel): per tile of 64 token rows
+ *   dy  = bf16(dh W1)                         the Linear's data gradient, bits of segf_gemm (layout 1) on these operands; never stored
+ *                                             unless dy_out (nullable, [rows][C]) asks for it
+ *   dx  = LN_bwd(dy) + dres                   bits of segf_layernorm_bwd_fused (dy2 == NULL) on that dy; dres nullable
+ *   dxs = (dt) dx * rscale[r / rows_per_group] (NULL, NULL: none) bits of segf_scale_rows on the stored dx; any rows < 2^31 (the group
+ *                                             index is an integer division here, so the 2^22 bound of segf_layernorm_bwd_scaled does not apply)
+ *   dw1 [N][C] = dh^T y, db1 [N] = colsum(dh), dgamma | dbeta [2][C]   fp32, from per-workgroup partials in fixed order (no atomics:
+ *                                             bitwise reproducible; NOT the summation order of segf_gemm_dw_db / segf_layernorm_bwd)
+ * dh, x (the LayerNorm's input), y (its saved output), dres, dx, dxs, dy_out: bf16, 16-byte aligned, dense rows; w1 bf16 [N][C] dense.
+ * dbeta == dgamma + C.  ws >= segf_layernorm_linear_bwd_ws(rows, C, N) floats.
+ * Deferred finalize: with dw1 == NULL (then db1, dgamma, dbeta NULL too) the partials stay in ws as three blocks
+ *   [nblk][N C] at ws, [nblk][N] at ws + nblk N C, [nblk][2 C] at ws + nblk (N C + N),   nblk = segf_layernorm_linear_bwd_blocks(rows),
+ * for three SegfFinalizeItem members of a later segf_colreduce_finalize_grouped call (the same sums as the immediate form).
+ * _supported: host arithmetic only; bf16, C in {32, 64}, N == 4 C, rows < 2^31 and SEGFAC_LN_LINEAR_BWD_FUSED (0 never, 1 from 131072
+ * rows on, 2 wherever the shape has the kernel).  The entry point itself checks the shape only: fp32 returns SEGF_ERR_DTYPE. */
+int segf_layernorm_linear_bwd_supported(int dt, int64_t rows, int C, int N);
+int segf_layernorm_linear_bwd_blocks(int64_t rows);
+int64_t segf_layernorm_linear_bwd_ws(int64_t rows, int C, int N);
+int segf_layernorm_linear_bwd(int dt, int64_t rows, int C, int N, const void* dh, const void* w1, const void* x, const void* y,
+                              const void* dres, const float* gamma, const float* mean, const float* rstd, void* dx,
+                              const float* rscale, int64_t rows_per_group, void* dxs, void* dy_out, float* dw1, float* db1,
+                              float* dgamma, float* dbeta, float* ws, void* stream);
 
 /* ---- BatchNorm2d (train: batch statistics) + ReLU/ReLU6 + Dropout2d, NHWC rows -------------------
  * ConvModule of heads/segformer.py:21-29, layers/conv_module.py:4-9, mobilenetv2.py:5-11.
@@ -707,6 +730,7 @@ int segf_input_val(const uint8_t* img, int64_t img_stride, const uint8_t* lbl, i
  *   SEGFAC_LOSS_NO_MFMA          ratio-4 loss kernels on the VALU cells form (fp32 storage)
  *   SEGFAC_LOSS_NO_RETRY         no exact per-pixel retry pass behind the flagged cells
  *   SEGFAC_LOSS_NO_LSE           the backward recomputes the softmax normalisation instead of taking the forward's per-pixel log-sum
+ *   SEGFAC_LN_LINEAR_BWD_FUSED   Mix-FFN backward, fc1's data / weight / bias gradients formed inside the LayerNorm backward of norm2 (segf_layernorm_linear_bwd_supported): 0 = never, 1 = from 131072 token rows on, 2 = wherever the shape has the kernel  (default 1)
  *   SEGFAC_NO_WIDE_FINALIZE      column-reduction finalize: one output per thread instead of four (bitwise the same sums)
  *   SEGFAC_NO_LN_PATCH           [host] MiT blocks: im2col / col2im around the spatial-reduction conv instead of the patch-major LayerNorm output
  *   SEGFAC_NO_SCALED_LN_BWD      [host] DropPath backward as its own scale_rows launch instead of riding on the LayerNorm backward

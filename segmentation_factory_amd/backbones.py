@@ -104,8 +104,8 @@ class MLP(nn.Module):
         self.fc2 = LinearWeights(c2, c1)
         self.apply(init_mit_style)
 
-    def tokens(self, h, B, H, W, residual, rscale):
-        f = Fh.linear(h, self.fc1.weight, self.fc1.bias)
+    def tokens(self, h, B, H, W, residual, rscale, hidden=False):
+        f = h if hidden else Fh.linear(h, self.fc1.weight, self.fc1.bias)          # hidden: h is fc1's output already
         dw = self.dwconv.dwconv
         if Fh.dwconv3x3_gelu_linear_ok(f, self.fc2.weight, self.fc2.bias, dw.weight, dw.bias, B, H, W):
             # large maps: one formula for dwconv + GELU -> fc2, whose backward never stores fc2's hidden-width data gradient
@@ -152,8 +152,10 @@ class Block(nn.Module):
         else:
             x, h = Fh.layer_norm_res(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)     # x passes through for the residual
             x = self.attn.tokens(h, B, H, W, x, s1)
-        x, h = Fh.layer_norm_res(x, self.norm2.weight, self.norm2.bias, self.norm2.eps)
-        return self.mlp.tokens(h, B, H, W, x, s2)
+        # norm2 -> mlp.fc1 as one formula where the fused backward exists (stages 1 / 2 on large maps), the two calls otherwise
+        fc1 = self.mlp.fc1
+        x, f = Fh.layer_norm_res_linear(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, fc1.weight, fc1.bias)
+        return self.mlp.tokens(f, B, H, W, x, s2, hidden=True)
 
 
 class MiT(nn.Module):

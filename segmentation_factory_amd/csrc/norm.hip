@@ -361,6 +361,380 @@ extern "C" int segf_colreduce_finalize_grouped(int n, const SegfFinalizeItem* it
     return 0;
 }
 
+// ---- fc1 data gradient + LayerNorm backward + fc1 weight / bias gradient in ONE streaming pass ------------------------------
+// The backward of `norm2 -> mlp.fc1` of a MiT block (mit.py:98,136-146) at C = 32 / 64, hidden width H = 4 C, as three launches reads
+// the hidden-width gradient dh twice and writes + re-reads the C-wide product dy = dh W1.  Here a
+// workgroup walks tiles of 64 token rows; the dh and y (saved LayerNorm output) rows of a tile are staged ONCE in LDS and
+//   * wave w forms dy^T = W1^T dh^T for its 16 tokens with the MFMA sequence of the kernel that forms it today (C = 32:
+//     gemm_skinny_kernel<1, 4, 2>, one chain over K ascending; C = 64: gemm_skinny_k_kernel<1, 2, 4>, four K-quarter chains
+//     from zero added in the order 0..3 -- or, below the row count from which segf_gemm takes that kernel, the one chain of the
+//     128-tile kernel: `ksplit`), rounds it to bf16 once, and applies ln_bwd_kernel's arithmetic to the rounded
+//     values: lane (mi, g) holds features 32 q + 8 g .. + 7 of token mi, so a token's chunks sit 16 lanes apart and the row
+//     sums run over them in wave_sum's pairing (xor 1, xor 2 on the chunk index, then xor 4 = the lane's own second chunk);
+//   * wave w accumulates rows [H / 4 w, H / 4 (w + 1)) of dW1 += dh^T y and db1 += colsum(dh) over all 64 tokens, both
+//     operands read transposed from the staged tiles (ds_read_b64_tr_b16), as gemm_dw_skinny_kernel does.
+// dW1, db1, dgamma, dbeta leave as per-workgroup fp32 partials (fixed order, no atomics) for the column-reduction finalize.
+// The next tile's rows are in flight in registers meanwhile; rows past the end: clamped loads, zeroed
+// staging (no contribution to dW1 / db1), masked LayerNorm sums and stores.
+#define LNL_MAX_BLOCKS 512          // 2 workgroups per CU (75 KB of LDS each at C = 64)
+typedef __attribute__((ext_vector_type(8))) __bf16 lnl_bf16x8;
+typedef __attribute__((ext_vector_type(4))) float lnl_f32x4;
+typedef __attribute__((ext_vector_type(4))) short lnl_s16x4;
+typedef __attribute__((ext_vector_type(8))) short lnl_s16x8;
+typedef uint32_t lnl_u32x4 __attribute__((ext_vector_type(4)));
+// 32 tokens x 16 features of a staged token-major tile as an MFMA fragment with the TOKENS along k (gemm.hip: frag_tok_tr)
+__device__ __forceinline__ lnl_bf16x8 lnl_frag_tok_tr(const unsigned char* tile, int rowbytes, int cb, int lane) {
+    const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
+    const unsigned char* a0 = tile + (8 * g + q) * rowbytes + (cb + 4 * p) * 2;
+    const lnl_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) lnl_s16x4*)a0);
+    const lnl_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) lnl_s16x4*)(a0 + 4 * rowbytes));
+    const lnl_s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    return __builtin_bit_cast(lnl_bf16x8, v);
+}
+// ln_bwd_kernel's per-chunk arithmetic for dx as that kernel's machine code performs it (the compiler keeps gy = dv * g and
+// gy * xh as rounded products and contracts gy - s1 - xh * s2 and the residual addition into fused multiply-adds): contraction is
+// off here and the fused operations are spelled out, so that the two kernels agree bit for bit whatever the optimiser would
+// choose for this one.
+// (xh and gy are formed twice, before and after the row sums, by the same operations on the same values: 32 registers fewer
+// across the sums at C = 64)
+__device__ __forceinline__ void lnl_chunk_sums(const float (&xv)[8], const float (&dv)[8], const float (&g)[8], float mu, float rs,
+                                               float (&xh)[8], float& s1, float& s2) {
+#pragma clang fp contract(off)
+    s1 = 0.f; s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        xh[j] = (xv[j] - mu) * rs;
+        const float gy = dv[j] * g[j];
+        s1 = s1 + gy;
+        const float p = gy * xh[j];
+        s2 = s2 + p;
+    }
+}
+__device__ __forceinline__ void lnl_chunk_out(const float (&xv)[8], const float (&dv)[8], const float (&g)[8], float mu, float s1, float s2,
+                                              float rs, bool has_res, const float (&res)[8], float (&o)[8]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float xh = (xv[j] - mu) * rs;
+        const float gy = dv[j] * g[j];
+        const float t = __builtin_fmaf(-s2, xh, gy - s1);
+        o[j] = has_res ? __builtin_fmaf(rs, t, res[j]) : rs * t;
+    }
+}
+__device__ __forceinline__ void lnl_unpack8(const lnl_u32x4 u, float (&v)[8]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { v[2 * j] = __uint_as_float(u[j] << 16); v[2 * j + 1] = __uint_as_float(u[j] & 0xffff0000u); }
+}
+__device__ __forceinline__ lnl_u32x4 lnl_pack8(const float (&v)[8]) {
+    lnl_u32x4 u;
+    u[0] = pack2bf(v[0], v[1]); u[1] = pack2bf(v[2], v[3]); u[2] = pack2bf(v[4], v[5]); u[3] = pack2bf(v[6], v[7]);
+    return u;
+}
+template <int KS> struct LnlGeom {
+    static constexpr int C = 32 * KS, H = 128 * KS;
+    static constexpr int RD = 2 * H + 16, RY = 2 * C + 16;               // staged row bytes (+16: bank spread)
+    static constexpr int NFRAG = 8 * KS * KS;                            // W1 fragments of 1 KB: [2 KS feature tiles][4 KS k-steps]
+    static constexpr int OFF_Y = 64 * RD, OFF_W = OFF_Y + 64 * RY, OFF_G = OFF_W + 1024 * NFRAG, LDS_BYTES = OFF_G + 4 * C;
+};
+template <int KS>
+__global__ void __launch_bounds__(256, 2) ln_linear_bwd_kernel(const bf16_t* __restrict__ dh, const bf16_t* __restrict__ w1 /*[4C][C]*/,
+                                                                const bf16_t* __restrict__ x, const bf16_t* __restrict__ y,
+                                                                const bf16_t* __restrict__ dres /*nullable*/, const float* __restrict__ gamma,
+                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                bf16_t* __restrict__ dx, const float* __restrict__ rsc /*nullable*/, uint32_t rpg,
+                                                                bf16_t* __restrict__ dxs, bf16_t* __restrict__ dyo /*nullable: the fc1 data gradient*/,
+                                                                float* __restrict__ pw /*[grid][4C][C]*/, float* __restrict__ pb /*[grid][4C]*/,
+                                                                float* __restrict__ pg /*[grid][2][C]*/, int64_t rows,
+                                                                int ksplit /*C = 64: K-quarter partials (else one chain over K)*/) {
+    typedef LnlGeom<KS> G;
+    constexpr int C = G::C, H = G::H, RD = G::RD, RY = G::RY;
+    constexpr int NT = 2 * KS;                                           // 16-feature tiles of dy
+    constexpr int NQ = KS == 1 ? 1 : 4, SPQ = KS == 1 ? 4 : 2;           // accumulation chains over K and 32-steps per chain
+    constexpr int ND = H / 32, NY = KS;                                  // 16-byte chunks per thread of a staged dh / y tile
+    extern __shared__ __attribute__((aligned(16))) unsigned char lnl_lds[];
+    unsigned char* dhs = lnl_lds;
+    unsigned char* ys = lnl_lds + G::OFF_Y;
+    unsigned char* wl = lnl_lds + G::OFF_W;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int mi = lane & 15, g = lane >> 4;
+    // W1 fragments in LDS, fragment (nt, ks) at 1 KB * (nt * 4 KS + ks): MFMA row i of tile nt carries feature
+    // 32 (nt >> 1) + 8 (i >> 2) + 4 (nt & 1) + (i & 3) and lane group g the k rows 32 ks + 8 g .. + 7 (gemm_skinny_kernel, LAYOUT 1)
+    for (int f = wave; f < G::NFRAG; f += 4) {
+        const int nt = f / (4 * KS), ks = f - nt * (4 * KS);
+        const int n = 32 * (nt >> 1) + 8 * (mi >> 2) + 4 * (nt & 1) + (mi & 3);
+        lnl_s16x8 w;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) w[j] = (short)w1[(32 * ks + 8 * g + j) * C + n];
+        *reinterpret_cast<lnl_s16x8*>(wl + 1024 * f + 16 * lane) = w;
+    }
+    float* gml = reinterpret_cast<float*>(lnl_lds + G::OFF_G);           // gamma, read back per tile (16 registers fewer at C = 64)
+    if (tid < C) gml[tid] = gamma[tid];
+    // dgamma / dbeta: a token's 16 lanes (one DPP row) sum each of the lane group's 8 KS features per tile, and lane mi keeps
+    // the running sum of feature 32 (mi >> 3) + 8 g + (mi & 7) -- two accumulators per lane instead of 16 KS
+    float accg = 0.f, accb = 0.f;
+    // this wave's [H / 4 x C] block of dW1; its db1 rows share ONE accumulator tile: row tile i is multiplied by a B fragment
+    // whose column i is all ones, so column i of the tile collects colsum(dh) of rows 16 i .. 16 i + 15
+    lnl_f32x4 aw[NT][NT], ab = lnl_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) aw[i][j] = lnl_f32x4{0.f, 0.f, 0.f, 0.f};
+    float bz = 0.f;                                                      // the absent bias of the data-gradient product (acc + 0, as that kernel adds it)
+    asm volatile("" : "+v"(bz));
+    const float invC = 1.f / (float)C;
+    const int64_t ntiles = (rows + 63) >> 6;
+    // staging: pass i of a thread takes chunk (tid % chunks per row) of row tid / (chunks per row) + i * (rows per pass) -- one
+    // column offset and one LDS address per thread, so that nothing per pass is kept across the loop
+    constexpr int CPD = H / 8, RPD = 256 / CPD, CPY = C / 8, RPY = 256 / CPY;
+    // Global addresses are a tile-uniform base (scalar registers) plus a 32-bit lane offset of the row within the tile, clamped
+    // to the tile's last existing row.
+    const int drow = tid / CPD, yrow = tid / CPY, dcol = 8 * (tid % CPD), ycol = 8 * (tid % CPY);
+    unsigned char* dst_d = dhs + drow * RD + 2 * dcol;
+    unsigned char* dst_y = ys + yrow * RY + 2 * ycol;
+    lnl_u32x4 rd[ND], ry[NY];
+    auto tile_last = [&](int64_t t) { const int64_t rem = rows - 1 - (t << 6); return (int)(rem < 63 ? rem : 63); };
+    auto load_tile = [&](int64_t t) {
+        const bf16_t* dht = dh + (t << 6) * H;
+        const bf16_t* yt = y + (t << 6) * C;
+        const int last = tile_last(t);
+#pragma unroll
+        for (int i = 0; i < ND; ++i) {
+            const int lr = drow + RPD * i < last ? drow + RPD * i : last;
+            rd[i] = *reinterpret_cast<const lnl_u32x4*>(dht + (uint32_t)(lr * H + dcol));
+        }
+#pragma unroll
+        for (int i = 0; i < NY; ++i) {
+            const int lr = yrow + RPY * i < last ? yrow + RPY * i : last;
+            ry[i] = *reinterpret_cast<const lnl_u32x4*>(yt + (uint32_t)(lr * C + ycol));
+        }
+    };
+    int64_t tile = blockIdx.x;
+    if (tile < ntiles) load_tile(tile);
+    for (; tile < ntiles; tile += gridDim.x) {
+        const int64_t r0 = tile << 6;
+        __syncthreads();                                                 // the previous tile's fragment reads (and the W1 fill) are complete
+        const lnl_u32x4 zero4 = {0u, 0u, 0u, 0u};
+        const int last = tile_last(tile);
+#pragma unroll
+        for (int i = 0; i < ND; ++i) *reinterpret_cast<lnl_u32x4*>(dst_d + RPD * i * RD) = drow + RPD * i <= last ? rd[i] : zero4;
+#pragma unroll
+        for (int i = 0; i < NY; ++i) *reinterpret_cast<lnl_u32x4*>(dst_y + RPY * i * RY) = yrow + RPY * i <= last ? ry[i] : zero4;
+        // this tile's LayerNorm operands of the lane's token
+        const int lrow = 16 * wave + mi;
+        const bool rv = lrow <= last;
+        const int lrc = rv ? lrow : last;
+        const uint32_t eo = (uint32_t)(lrc * C + 8 * g);                 // the lane's first chunk, elements from the tile's first row
+        const bf16_t* xt = x + r0 * C;
+        const bf16_t* rt = dres + r0 * C;
+        lnl_u32x4 rx[KS], rr[KS];
+#pragma unroll
+        for (int q = 0; q < KS; ++q) {
+            rx[q] = *reinterpret_cast<const lnl_u32x4*>(xt + (eo + 32 * q));
+            if (dres) rr[q] = *reinterpret_cast<const lnl_u32x4*>(rt + (eo + 32 * q));
+        }
+        const float mu = (mean + r0)[lrc], rs = rv ? (rstd + r0)[lrc] : 0.f;
+        float sc = 0.f;
+        if (dxs) sc = rsc[(uint32_t)(r0 + lrc) / rpg];
+        // The next tile's rows (unconditional: the last one re-reads).  C = 32 requests them here, a whole tile ahead; at C = 64 the 40
+        // registers they land in are not free across the two phases below (the kernel spilled), so there they are requested
+        // behind the LayerNorm phase and land during the weight-gradient products and the other workgroup's turn.
+        const int64_t nxt = tile + gridDim.x < ntiles ? tile + gridDim.x : tile;
+        if (KS == 1) load_tile(nxt);
+        SEGF_LOADS_ISSUED();
+        __syncthreads();
+        // ---- data gradient of the wave's 16 tokens: dy^T = W1^T dh^T, the dh rows as the B operand as they lie
+        float dyv[KS][8];
+        {
+            lnl_f32x4 sum[NT];
+            const unsigned char* brow = dhs + (16 * wave + mi) * RD + 16 * g;
+            // (a rolled loop over the K quarters: unrolled, the scheduler lifts all 32 fragment reads of C = 64 above the first product
+            // and the kernel spills)
+#pragma unroll 1
+            for (int kq = 0; kq < NQ; ++kq) {
+                lnl_bf16x8 xa[SPQ];
+#pragma unroll
+                for (int s = 0; s < SPQ; ++s) xa[s] = *reinterpret_cast<const lnl_bf16x8*>(brow + 64 * (kq * SPQ + s));
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    lnl_f32x4 a = lnl_f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (kq != 0 && !ksplit) a = sum[nt];                 // one chain over all of K
+#pragma unroll
+                    for (int s = 0; s < SPQ; ++s) {
+                        const lnl_bf16x8 wf = *reinterpret_cast<const lnl_bf16x8*>(wl + 1024 * (nt * 4 * KS + kq * SPQ + s) + 16 * lane);
+                        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xa[s], a, 0, 0, 0);
+                    }
+                    if (kq == 0 || !ksplit) sum[nt] = a; else sum[nt] = sum[nt] + a;
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int q = 0; q < KS; ++q)
+#pragma unroll
+                for (int rr_ = 0; rr_ < 4; ++rr_) { dyv[q][rr_] = sum[2 * q][rr_] + bz; dyv[q][4 + rr_] = sum[2 * q + 1][rr_] + bz; }
+        }
+        // ---- LayerNorm backward on the bf16-rounded dy
+        {
+            lnl_u32x4 dp[KS];
+            float s1[KS], s2[KS];
+#pragma unroll
+            for (int q = 0; q < KS; ++q) {
+                dp[q] = lnl_pack8(dyv[q]);
+                if (dyo && rv) *reinterpret_cast<lnl_u32x4*>(dyo + r0 * C + (eo + 32 * q)) = dp[q];
+                if (!rv) dp[q] = lnl_u32x4{0u, 0u, 0u, 0u};              // (rs == 0 too: xh = 0, nothing reaches dgamma / dbeta)
+                float xv[8], dv[8], gm[8], xh[8];
+                lnl_unpack8(rx[q], xv);
+                lnl_unpack8(dp[q], dv);
+                load8f(gml + 32 * q + 8 * g, gm);
+                lnl_chunk_sums(xv, dv, gm, mu, rs, xh, s1[q], s2[q]);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float ag = wave_sum(dv[j] * xh[j], 16), abt = wave_sum(dv[j], 16);
+                    if (mi == 8 * q + j) { accg += ag; accb += abt; }
+                }
+                s1[q] += __shfl_xor(s1[q], 16, 64); s1[q] += __shfl_xor(s1[q], 32, 64);
+                s2[q] += __shfl_xor(s2[q], 16, 64); s2[q] += __shfl_xor(s2[q], 32, 64);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            float t1 = s1[0], t2 = s2[0];
+            if (KS == 2) { t1 += s1[KS - 1]; t2 += s2[KS - 1]; }
+            t1 *= invC; t2 *= invC;
+#pragma unroll
+            for (int q = 0; q < KS; ++q) {
+                float xv[8], dv[8], gm[8], o[8], res[8];
+                lnl_unpack8(rx[q], xv);
+                lnl_unpack8(dp[q], dv);
+                load8f(gml + 32 * q + 8 * g, gm);
+                if (dres) lnl_unpack8(rr[q], res);
+                else {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) res[j] = 0.f;
+                }
+                lnl_chunk_out(xv, dv, gm, mu, t1, t2, rs, dres != nullptr, res, o);
+                const lnl_u32x4 op = lnl_pack8(o);
+                if (rv) *reinterpret_cast<lnl_u32x4*>(dx + r0 * C + (eo + 32 * q)) = op;
+                if (dxs) {
+                    float ov[8];
+                    lnl_unpack8(op, ov);                                 // the STORED dx (rounded), as segf_scale_rows reads it
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) ov[j] *= sc;
+                    if (rv) *reinterpret_cast<lnl_u32x4*>(dxs + r0 * C + (eo + 32 * q)) = lnl_pack8(ov);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (KS != 1) load_tile(nxt);
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- dW1 += dh^T y, db1 += colsum(dh): rows [H / 4 wave, + H / 4) over the tile's 64 tokens (two k-steps of 32)
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            lnl_bf16x8 fa[NT];
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+                fa[i] = lnl_frag_tok_tr(dhs + kk * 32 * RD, RD, (H / 4) * wave + 16 * i, lane);
+                uint32_t one2 = mi == i ? 0x3f803f80u : 0u;
+                asm volatile("" : "+v"(one2));                           // (built here: kept across the loop the four selectors are 16 registers)
+                const lnl_u32x4 sel = {one2, one2, one2, one2};
+                ab = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], __builtin_bit_cast(lnl_bf16x8, sel), ab, 0, 0, 0);
+            }
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                const lnl_bf16x8 fb = lnl_frag_tok_tr(ys + kk * 32 * RY, RY, 16 * j, lane);
+#pragma unroll
+                for (int i = 0; i < NT; ++i) aw[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, aw[i][j], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    // ---- partials.  accumulator (i, j): rows H / 4 wave + 16 i + 4 g + r, column 16 j + mi
+    float* pwb = pw + (int64_t)blockIdx.x * H * C;
+    float* pbb = pb + (int64_t)blockIdx.x * H;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+#pragma unroll
+        for (int rr_ = 0; rr_ < 4; ++rr_) {
+            const int m = (H / 4) * wave + 16 * i + 4 * g + rr_;
+#pragma unroll
+            for (int j = 0; j < NT; ++j) pwb[m * C + 16 * j + mi] = aw[i][j][rr_];
+        }
+    }
+    if (mi < NT) {
+#pragma unroll
+        for (int rr_ = 0; rr_ < 4; ++rr_) pbb[(H / 4) * wave + 16 * mi + 4 * g + rr_] = ab[rr_];
+    }
+    // dgamma / dbeta: across the waves through LDS in fixed order
+    __syncthreads();
+    float* red = reinterpret_cast<float*>(dhs);                          // [4 waves][2][C]
+    if (mi < 8 * KS) {
+        red[(wave * 2 + 0) * C + 32 * (mi >> 3) + 8 * g + (mi & 7)] = accg;
+        red[(wave * 2 + 1) * C + 32 * (mi >> 3) + 8 * g + (mi & 7)] = accb;
+    }
+    __syncthreads();
+    if (tid < 2 * C) {
+        float s = 0.f;
+        for (int w = 0; w < 4; ++w) s += red[w * 2 * C + tid];
+        pg[(int64_t)blockIdx.x * 2 * C + tid] = s;
+    }
+}
+
+static inline int lnl_blocks(int64_t rows) { return (int)imin64(cdiv64(rows, 64), LNL_MAX_BLOCKS); }
+// The shapes the fused form exists for and the sizes the policy sends to it (SEGFAC_LN_LINEAR_BWD_FUSED: 0 never, 1 from 131072 token
+// rows on -- the recorded batch-4 step keeps its three launches --, 2 wherever the shape has the kernel)
+extern "C" int segf_layernorm_linear_bwd_supported(int dt, int64_t rows, int C, int N) {
+    const int pol = POL(ln_linear_bwd_fused);
+    if (pol <= 0 || dt != SEGF_BF16 || (C != 32 && C != 64) || N != 4 * C) return 0;
+    if (rows <= 0 || rows > 0x7fffffffll) return 0;
+    return (pol >= 2 || rows >= 131072) ? 1 : 0;
+}
+extern "C" int segf_layernorm_linear_bwd_blocks(int64_t rows) { return rows > 0 ? lnl_blocks(rows) : 0; }
+extern "C" int64_t segf_layernorm_linear_bwd_ws(int64_t rows, int C, int N) {
+    return rows > 0 ? (int64_t)lnl_blocks(rows) * ((int64_t)N * C + N + 2 * C) : 0;
+}
+extern "C" int segf_layernorm_linear_bwd(int dt, int64_t rows, int C, int N, const void* dh, const void* w1, const void* x, const void* y,
+                                         const void* dres, const float* gamma, const float* mean, const float* rstd, void* dx,
+                                         const float* rscale, int64_t rows_per_group, void* dxs, void* dy_out, float* dw1, float* db1,
+                                         float* dgamma, float* dbeta, float* ws, void* stream) {
+    if (dt != SEGF_BF16) return SEGF_ERR_DTYPE;
+    if ((C != 32 && C != 64) || N != 4 * C || rows <= 0 || rows > 0x7fffffffll) return SEGF_ERR_SHAPE;
+    if ((rscale != nullptr) != (dxs != nullptr)) return SEGF_ERR_SHAPE;
+    if (rscale && (rows_per_group <= 0 || rows_per_group > 0x7fffffffll)) return SEGF_ERR_SHAPE;
+    if (((uintptr_t)dh % 16) || ((uintptr_t)w1 % 2) || ((uintptr_t)x % 16) || ((uintptr_t)y % 16) || ((uintptr_t)dres % 16) ||
+        ((uintptr_t)gamma % 16) || ((uintptr_t)dx % 16) || ((uintptr_t)dxs % 16) || ((uintptr_t)dy_out % 16)) return SEGF_ERR_SHAPE;
+    if (!ws) return SEGF_ERR_WORKSPACE;
+    const bool now = dw1 != nullptr;                                     // NULL: deferred finalize (segf_colreduce_finalize_grouped on the three partial blocks)
+    if (now ? (!db1 || !dgamma || dbeta != dgamma + C) : (db1 || dgamma || dbeta)) return SEGF_ERR_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = lnl_blocks(rows);
+    float* pw = ws;
+    float* pb = pw + (int64_t)blocks * N * C;
+    float* pg = pb + (int64_t)blocks * N;
+    const uint32_t rpg = rscale ? (uint32_t)rows_per_group : 1u;
+    // the order in which segf_gemm (layout 1) sums K = 256 at this row count: gemm_skinny_k_kernel's quarters from 65536 rows on
+    // (gemm.hip: gemm_skinny_k_ok), one chain on the 128-tile kernel below
+    const int ksplit = C == 64 && rows >= 65536 && !POL(gemm_no_skinny_k) && !POL(gemm_no_skinny);
+    // C = 64 stages 75 KB: above the 64 KB a kernel gets by default, so the limit is raised on the function, once per device
+#define LNL(KS_) do { \
+        static int lds_dev = -1; \
+        int dev = -1; \
+        if (LnlGeom<KS_>::LDS_BYTES > 65536 && !segf_trace().dry && hipGetDevice(&dev) == hipSuccess && dev != lds_dev) { \
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ln_linear_bwd_kernel<KS_>), hipFuncAttributeMaxDynamicSharedMemorySize, LnlGeom<KS_>::LDS_BYTES) != hipSuccess) return SEGF_ERR_SHAPE; \
+            lds_dev = dev; \
+        } \
+        hipLaunchKernelGGL((ln_linear_bwd_kernel<KS_>), dim3(blocks), dim3(256), LnlGeom<KS_>::LDS_BYTES, st, (const bf16_t*)dh, (const bf16_t*)w1, (const bf16_t*)x, \
+                           (const bf16_t*)y, (const bf16_t*)dres, gamma, mean, rstd, (bf16_t*)dx, rscale, rpg, (bf16_t*)dxs, (bf16_t*)dy_out, pw, pb, pg, rows, ksplit); } while (0)
+    if (C == 32) LNL(1); else LNL(2);
+#undef LNL
+    SEGF_CHECK_LAUNCH();
+    if (!now) return 0;
+    colreduce_finalize_launch(pw, blocks, (int64_t)N * C, dw1, st);
+    SEGF_CHECK_LAUNCH();
+    colreduce_finalize_launch(pb, blocks, N, db1, st);
+    SEGF_CHECK_LAUNCH();
+    colreduce_finalize_launch(pg, blocks, 2 * (int64_t)C, dgamma, st);
+    SEGF_CHECK_LAUNCH();
+    return 0;
+}
+
 // ---- BatchNorm on NHWC rows ---------------------------------------------------------------------------------
 // Accuracy of the statistics: the variance is E[x^2] - mean^2 from fp32 sums of x and x^2 (combined in double), so it is as accurate as
 // those sums allow and its relative error grows as (mean / sigma)^2 (tests/test_norm_float64.py pins this).

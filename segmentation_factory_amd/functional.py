@@ -591,6 +591,84 @@ def layer_norm_res(x, gamma, beta, eps):
     return LayerNormResFn.apply(x, gamma, beta, eps, *_dp_of(x))
 
 
+@direct_grads(1, 2, 4, 5)
+class LayerNormResLinearFn(Function):
+    """(x, Linear(LayerNorm(x))): the pre-norm residual pattern of LayerNormResFn with the norm's only consumer, a C -> 4 C Linear (norm2 ->
+    mlp.fc1 of a MiT block, mit.py:98,136-146), inside the same formula, so that the backward never writes the Linear's C-wide data gradient
+    and reads the hidden-width gradient once: hip.layernorm_linear_bwd forms dy = dh W1, the LayerNorm backward of it and the four
+    parameter gradients in one pass.  The forward makes the two calls LayerNormResFn and LinearFn make; dx (and the DropPath-scaled copy
+    parked for the producer of x) carry the bits of that pair, the parameter gradients are the same sums in another order.  The choice of
+    this formula is made at forward time (layer_norm_res_linear_ok)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, weight, bias, dp_scale=None, dp_rpg=1):
+        ctx.dp = (dp_scale, int(dp_rpg)) if dp_scale is not None else None
+        x = x if x.is_contiguous() else x.contiguous()
+        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        y, mean, rstd = hip.layernorm_fwd(x, g, b, eps)
+        M, K = x.shape
+        N = weight.shape[0]
+        w = _w(weight.reshape(N, -1), x.dtype)
+        h = hip.gemm(0, y, w, M, N, K, bias=bias.detach())
+        ctx.save_for_backward(x, g, mean, rstd, y, w)
+        ctx.wshape = weight.shape
+        return x.view_as(x), h
+
+    @staticmethod
+    def backward(ctx, dres, dh):
+        x, g, mean, rstd, y, w = ctx.saved_tensors
+        if dh is None:
+            return dres, None, None, None, None, None, None, None
+        dh = dh if dh.is_contiguous() else dh.contiguous()
+        if dres is not None and not dres.is_contiguous():
+            dres = dres.contiguous()
+        N, K = w.shape
+        rscale, rpg = ctx.dp if ctx.dp is not None else (None, 1)
+        gg, gb, gw, gb1 = gslot(ctx, 1), gslot(ctx, 2), gslot(ctx, 4), gslot(ctx, 5)
+        outs = None
+        if (gg is not None and gb is not None and gw is not None and gb1 is not None and gb.data_ptr() == gg.data_ptr() + 4 * gg.numel()
+                and gw.is_contiguous() and gb1.is_contiguous()):
+            outs = (gw.view(N, K), gb1, gg, gb)
+        q = _FIN_QUEUE
+        if q is not None and outs is not None:
+            slots = ctx._gslots
+            dx, items = hip.layernorm_linear_bwd(dh, w, x, y, g, mean, rstd, dres=dres, rscale=rscale, rows_per_group=rpg, outs=outs, defer=True)
+            q.append((items[0], (slots[4],)))
+            q.append((items[1], (slots[5],)))
+            q.append((items[2], (slots[1], slots[2])))
+            if len(q) >= FIN_QUEUE_MAX:
+                _flush_finalizes()
+            res = (dx, None, None, None, None, None, None, None)
+        else:
+            dx, dw, db1, dg, db = hip.layernorm_linear_bwd(dh, w, x, y, g, mean, rstd, dres=dres, rscale=rscale, rows_per_group=rpg, outs=outs)
+            res = (dx, dg, db, None, dw.view(ctx.wshape), db1, None, None)
+        if getattr(dx, 'scaled', None) is not None:          # parked for the backward of x's producer, as _ln_bwd parks it
+            if len(_SCALED_DY) > 64:
+                _SCALED_DY.clear()
+            _SCALED_DY[dx.data_ptr()] = (dx.scaled, rscale.data_ptr(), rpg, dx._version)
+            dx.scaled = None
+        return res
+
+
+def layer_norm_res_linear_ok(x, gamma, beta, weight, bias):
+    """May (x, Linear(LayerNorm(x))) run as LayerNormResLinearFn?  The library's shape / size / policy rule
+    (segf_layernorm_linear_bwd_supported), a training pass, and all four parameters present and trained."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.ndim == 2 and torch.is_grad_enabled() and x.requires_grad):
+        return False
+    if bias is None or weight.ndim != 2 or not all(p.requires_grad for p in (gamma, beta, weight, bias)):
+        return False
+    return hip.layernorm_linear_bwd_supported(x.dtype, x.shape[0], x.shape[1], weight.shape[0])
+
+
+def layer_norm_res_linear(x, gamma, beta, eps, weight, bias):
+    """-> (x, Linear(LayerNorm(x))): use the returned x for the residual connection.  One formula where the fused backward exists for the
+    shape (layer_norm_res_linear_ok), layer_norm_res + linear otherwise -- the same forward calls either way."""
+    if layer_norm_res_linear_ok(x, gamma, beta, weight, bias):
+        return LayerNormResLinearFn.apply(x, gamma, beta, eps, weight, bias, *_dp_of(x))
+    x, h = layer_norm_res(x, gamma, beta, eps)
+    return x, linear(h, weight, bias)
+
+
 @direct_grads(1, 2)
 class LayerNormResPatchFn(Function):
     """LayerNormResFn for the norm in front of a MiT attention with spatial reduction (mit.py:143, 47): besides (x, norm(x)) it returns

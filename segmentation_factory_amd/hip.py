@@ -770,6 +770,56 @@ def layernorm_bwd(x, dy, gamma, mean, rstd, dgb_out=None, dy2=None, dres=None, d
     return dx, dg, db
 
 
+def layernorm_linear_bwd_supported(dtype, rows, Cc, N):
+    """May the backward of LayerNorm(C) -> Linear(C, N) run as one pass (segf_layernorm_linear_bwd)?  Shape, size and policy rule of the
+    library (SEGFAC_LN_LINEAR_BWD_FUSED)."""
+    if dtype not in (torch.bfloat16, torch.float32):
+        return False
+    return bool(lib().segf_layernorm_linear_bwd_supported(BF16 if dtype == torch.bfloat16 else F32, int(rows), int(Cc), int(N)))
+
+
+def layernorm_linear_bwd(dh, w1, x, y, gamma, mean, rstd, dres=None, rscale=None, rows_per_group=1, outs=None, defer=False, return_dy=False):
+    """dh [rows, N] bf16: gradient of Linear(LayerNorm(x)) with w1 [N, C] bf16, y = the saved LayerNorm output.
+    -> (dx, dw1, db1, dgamma, dbeta) with the parameter gradients fp32; `dx.scaled` = dx * rscale[row / rows_per_group] when rscale is given.
+    outs = (dw1 [N, C], db1 [N], dgamma [C], dbeta [C]) fp32 targets written in place (dbeta adjacent to dgamma: dbeta == dgamma + C).
+    defer=True (needs outs): the kernel leaves its per-workgroup partial sums and (dx, [three finalize items]) is returned; the caller
+    passes the items to colreduce_finalize_grouped later.  return_dy: the Linear's data gradient [rows, C] is appended to the result."""
+    rows, Cc = x.shape
+    N = w1.shape[0]
+    _need_cuda(dh, w1, x, y, gamma, mean, rstd)
+    assert dh.shape == (rows, N) and w1.shape == (N, Cc) and y.shape == x.shape
+    assert all(t.dtype == torch.bfloat16 and t.is_contiguous() for t in (dh, w1, x, y))
+    assert dres is None or (dres.shape == x.shape and dres.dtype == x.dtype and dres.is_contiguous())
+    dx = torch.empty_like(x)
+    dxs = None
+    if rscale is not None:
+        _need_cuda(rscale)
+        assert rscale.dtype == torch.float32 and rscale.is_contiguous() and rscale.numel() * rows_per_group >= rows
+        dxs = torch.empty_like(x)
+    dyo = torch.empty_like(x) if return_dy else None
+    if outs is not None:
+        dw, db1, dg, db = outs
+        assert all(t.dtype == torch.float32 and t.is_contiguous() for t in outs)
+        assert dw.numel() == N * Cc and db1.numel() == N and dg.numel() == Cc and db.numel() == Cc and db.data_ptr() == dg.data_ptr() + 4 * Cc
+    else:
+        assert not defer
+        dw = torch.empty((N, Cc), dtype=torch.float32, device=x.device)
+        db1 = torch.empty(N, dtype=torch.float32, device=x.device)
+        dgb = torch.empty((2, Cc), dtype=torch.float32, device=x.device)
+        dg, db = dgb[0], dgb[1]
+    ws = _f32(lib().segf_layernorm_linear_bwd_ws(rows, Cc, N), x.device)
+    now = [None] * 4 if defer else [dw.data_ptr(), db1.data_ptr(), dg.data_ptr(), db.data_ptr()]
+    _chk(lib().segf_layernorm_linear_bwd(dt_of(x), rows, Cc, N, _ptr(dh), _ptr(w1), _ptr(x), _ptr(y), _ptr(dres), _ptr(gamma), _ptr(mean),
+                                         _ptr(rstd), _ptr(dx), _ptr(rscale), int(rows_per_group), _ptr(dxs), _ptr(dyo), *now, _ptr(ws),
+                                         _stream()), 'segf_layernorm_linear_bwd')
+    dx.scaled = dxs
+    if defer:
+        nblk = int(lib().segf_layernorm_linear_bwd_blocks(rows))
+        items = [(ws, nblk, N * Cc, dw), (ws[nblk * N * Cc:], nblk, N, db1), (ws[nblk * (N * Cc + N):], nblk, 2 * Cc, dg)]
+        return (dx, items, dyo) if return_dy else (dx, items)
+    return (dx, dw, db1, dg, db, dyo) if return_dy else (dx, dw, db1, dg, db)
+
+
 def bn_stats(x, running_mean, running_var, momentum, eps):
     rows, Cc = x.shape
     mean = torch.empty(Cc, dtype=torch.float32, device=x.device)
