@@ -263,6 +263,34 @@ int segf_layernorm_linear_bwd(int dt, int64_t rows, int C, int N, const void* dh
                               const void* dres, const float* gamma, const float* mean, const float* rstd, void* dx,
                               const float* rscale, int64_t rows_per_group, void* dxs, void* dy_out, float* dw1, float* db1,
                               float* dgamma, float* dbeta, float* ws, void* stream);
+/* The general form (csrc/norm.hip: ln_linear_bwd_kernel<KS, true, HM, FAN>), N = 4 C or N = C (the attention's q Linear behind norm1):
+ *   y == NULL   the LayerNorm output is REBUILT from x, mean, rstd, gamma and beta (bits of segf_layernorm_fwd: dw1 does not change), so the
+ *               forward keeps no y; y != NULL: N == 4 C only, segf_layernorm_linear_bwd itself
+ *   dy2         (nullable, N == C only) a second consumer's gradient of the LayerNorm output, added to the bf16-rounded dy on load as
+ *               segf_layernorm_bwd_patch adds it: patch-major row order with log2_w >= 0 (segf_layernorm_fwd_patch's y2), token order with < 0
+ * Everything else as segf_layernorm_linear_bwd (same workspace layout with this N, same deferred finalize).
+ * _ex_supported: bf16, C in {32, 64}, N in {C, 4 C}, rows < 2^31 and SEGFAC_LN_LINEAR_BWD_FUSED. */
+int segf_layernorm_linear_bwd_ex_supported(int dt, int64_t rows, int C, int N);
+int segf_layernorm_linear_bwd_ex(int dt, int64_t rows, int C, int N, const void* dh, const void* w1, const void* x, const void* y,
+                                 const float* beta, const void* dy2, int log2_w, int log2_sr, const void* dres, const float* gamma,
+                                 const float* mean, const float* rstd, void* dx, const float* rscale, int64_t rows_per_group, void* dxs,
+                                 void* dy_out, float* dw1, float* db1, float* dgamma, float* dbeta, float* ws, void* stream);
+/* `LayerNorm -> Linear` forward in ONE pass at C = 32 / 64, N = C or 4 C, bias present (norm1 -> attn.q, norm2 -> mlp.fc1 of a MiT block,
+ * mit.py:45,98,136-146; csrc/norm.hip: ln_linear_fwd_kernel): the rows of x are normalised in registers and the bf16-rounded result is the
+ * operand of the streaming product, so the C-wide LayerNorm output is neither written nor read back.
+ *   out [rows][N] = bf16(y w^T + bias)   bits of segf_gemm (layout 0) on the y of segf_layernorm_fwd
+ *   mean, rstd [rows]                    bits of segf_layernorm_fwd
+ *   y  (nullable, [rows][C])             the LayerNorm output in token order, bits of segf_layernorm_fwd (only where a consumer still reads it)
+ *   y2 (nullable)                        ... in patch-major row order: the arguments y2, log2_w, log2_sr of segf_layernorm_fwd_patch
+ * x, out, y, y2: bf16, 16-byte aligned, dense rows; w bf16 [N][C] dense, 16-byte aligned; gamma, beta fp32 [C] 16-byte aligned; bias fp32 [N].
+ * _supported: host arithmetic only; bf16, C in {32, 64}, N in {C, 4 C}, rows < 2^31 and SEGFAC_LN_LINEAR_FWD_FUSED (0 never, 1 from 131072
+ * rows on, 2 wherever the shape has the kernel).  The entry point itself checks the shape only: fp32 returns SEGF_ERR_DTYPE.
+ * _blocks: the workgroups the launch takes, min(ceil(ceil(rows / 16) / 16), 2048). */
+int segf_layernorm_linear_fwd_supported(int dt, int64_t rows, int C, int N);
+int segf_layernorm_linear_fwd_blocks(int64_t rows);
+int segf_layernorm_linear_fwd(int dt, int64_t rows, int C, int N, const void* x, const float* gamma, const float* beta, float eps,
+                              const void* w, const float* bias, void* out, float* mean, float* rstd, void* y, void* y2, int log2_w,
+                              int log2_sr, void* stream);
 
 /* ---- BatchNorm2d (train: batch statistics) + ReLU/ReLU6 + Dropout2d, NHWC rows -------------------
  * ConvModule of heads/segformer.py:21-29, layers/conv_module.py:4-9, mobilenetv2.py:5-11.
@@ -707,7 +735,7 @@ int segf_input_val(const uint8_t* img, int64_t img_stride, const uint8_t* lbl, i
  *   SEGFAC_NO_FP8_CONV           segf_conv3x3_fp8*_supported answer 0
  *   SEGFAC_NO_FP8_WGRAD          fp8 3 x 3 convolutions keep a bf16 weight gradient
  *   SEGFAC_NO_FP8_LINEAR         segf_linear_fp8_supported answers 0
- *   SEGFAC_DILCONV_NO_CULL       dilated 3 x 3 convolution (segf_conv3x3_dil): all nine taps are walked, with zero loads where a tap leaves the image
+ *   SEGFAC_DILCONV_NO_CULL       dilated 3 x 3 convolution: all nine taps are walked, with zero loads where a tap leaves the image, instead of the live taps only
  *   SEGFAC_ATTN_NO_MFMA          attention on the VALU reference kernels (attention.hip) also in bf16
  *   SEGFAC_ATTN_F32_NO_MFMA      fp32 attention forward on the vector kernel (one query per lane) instead of the f32 matrix instruction
  *   SEGFAC_ATTN64_PRESCALE       head dim 64, >= 128 keys: scale log2(e) rides on the Q fragments (bf16(q c), one more rounding per q element) and -max / -lse are the score accumulators' initial values, instead of one multiply-add per score: forward + query-side backward, +8 % / +2 % per kernel, attention error x 1.2 - 2.3
@@ -731,6 +759,7 @@ int segf_input_val(const uint8_t* img, int64_t img_stride, const uint8_t* lbl, i
  *   SEGFAC_LOSS_NO_RETRY         no exact per-pixel retry pass behind the flagged cells
  *   SEGFAC_LOSS_NO_LSE           the backward recomputes the softmax normalisation instead of taking the forward's per-pixel log-sum
  *   SEGFAC_LN_LINEAR_BWD_FUSED   Mix-FFN backward, fc1's data / weight / bias gradients formed inside the LayerNorm backward of norm2 (segf_layernorm_linear_bwd_supported): 0 = never, 1 = from 131072 token rows on, 2 = wherever the shape has the kernel  (default 1)
+ *   SEGFAC_LN_LINEAR_FWD_FUSED   MiT stages 1 / 2: LayerNorm as the operand prologue of its thin Linear (norm2 -> fc1, norm1 -> q; segf_layernorm_linear_fwd_supported), the LayerNorm output neither stored nor saved, and norm1 -> q's backward in one pass where SEGFAC_LN_LINEAR_BWD_FUSED allows it too: 0 = never, 1 = from 131072 token rows on, 2 = wherever the shape has the kernel  (default 1)
  *   SEGFAC_NO_WIDE_FINALIZE      column-reduction finalize: one output per thread instead of four (bitwise the same sums)
  *   SEGFAC_NO_LN_PATCH           [host] MiT blocks: im2col / col2im around the spatial-reduction conv instead of the patch-major LayerNorm output
  *   SEGFAC_NO_SCALED_LN_BWD      [host] DropPath backward as its own scale_rows launch instead of riding on the LayerNorm backward

@@ -61,13 +61,15 @@ class Attention(nn.Module):
             self.norm = LayerNormWeights(dim)
         self.apply(init_mit_style)
 
-    def tokens(self, h, B, H, W, residual, rscale, col=None):
+    def tokens(self, h, B, H, W, residual, rscale, col=None, q=None):
         N = H * W
         if col is not None:
             # the norm in front already wrote its output as the im2col matrix of the spatial-reduction convolution (layer_norm_res_patch):
             # no im2col / col2im passes, and the two consumers' gradients meet in the LayerNorm backward
+            # (q given: the norm formed the q Linear's output as well -- layer_norm_res_patch_linear -- and h is None)
             sr = self.sr_ratio
-            q = Fh.linear(h, self.q.weight, self.q.bias)
+            if q is None:
+                q = Fh.linear(h, self.q.weight, self.q.bias)
             xr = Fh.conv_from_col(col, self.sr.weight, self.sr.bias, sr)
             xr = Fh.layer_norm(xr, self.norm.weight, self.norm.bias, self.norm.eps)
             Nkv = (H // sr) * (W // sr)
@@ -147,8 +149,14 @@ class Block(nn.Module):
         s1, s2 = scales
         sr = self.attn.sr_ratio
         if Fh.patch_layout_ok(W, H, sr) and x.is_cuda:
-            x, h, col = Fh.layer_norm_res_patch(x, self.norm1.weight, self.norm1.bias, self.norm1.eps, W, sr)
-            x = self.attn.tokens(h, B, H, W, x, s1, col=col)
+            qw = self.attn.q
+            if Fh.layer_norm_res_patch_linear_ok(x, self.norm1.weight, self.norm1.bias, qw.weight, qw.bias):
+                # stages 1 / 2 on large maps: norm1 -> q as one formula (the token-order LayerNorm output is never stored)
+                x, q, col = Fh.layer_norm_res_patch_linear(x, self.norm1.weight, self.norm1.bias, self.norm1.eps, W, sr, qw.weight, qw.bias)
+                x = self.attn.tokens(None, B, H, W, x, s1, col=col, q=q)
+            else:
+                x, h, col = Fh.layer_norm_res_patch(x, self.norm1.weight, self.norm1.bias, self.norm1.eps, W, sr)
+                x = self.attn.tokens(h, B, H, W, x, s1, col=col)
         else:
             x, h = Fh.layer_norm_res(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)     # x passes through for the residual
             x = self.attn.tokens(h, B, H, W, x, s1)

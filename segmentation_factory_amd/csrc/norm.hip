@@ -3,6 +3,8 @@
 //   LayerNorm: reference nn.LayerNorm in models/backbones/mit.py:107,129,136-140 (eps 1e-5) and the
 //              channels-first LayerNorm of convnext.py:8-23 / convnextv2.py:40-66 (eps 1e-6).
 //   BatchNorm: ConvModule of heads/segformer.py:21-29, layers/conv_module.py:4-9, mobilenetv2.py:5-11.
+#include <type_traits>
+
 #include "colreduce.h"
 
 // ---- LayerNorm -----------------------------------------------------------------------------------------
@@ -430,27 +432,44 @@ __device__ __forceinline__ lnl_u32x4 lnl_pack8(const float (&v)[8]) {
     u[0] = pack2bf(v[0], v[1]); u[1] = pack2bf(v[2], v[3]); u[2] = pack2bf(v[4], v[5]); u[3] = pack2bf(v[6], v[7]);
     return u;
 }
-template <int KS> struct LnlGeom {
-    static constexpr int C = 32 * KS, H = 128 * KS;
+// The same pass in three more forms (template arguments behind KS; the three-argument-less spelling is the form above):
+//   YX   the LayerNorm output is not read but REBUILT from the x rows, mean, rstd the kernel loads anyway: y = bf16(fma(gamma, xh, beta)) with
+//        xh = (x - mean) * rstd -- ln_fwd_kernel's operations (its gfx950 code: subtract, multiply, one fused multiply-add, one rounding), so
+//        the staged tile holds the bits that kernel stored and dW1 does not change.  The wave's 16 token rows go to LDS behind the LayerNorm
+//        phase (one more barrier per tile); nothing else is staged for y.
+//   HM   hidden width H = HM * C: 4 (mlp.fc1) or 1 (the attention's q Linear behind norm1, mit.py:45,143: ONE row of W fragments, one chain over
+//        K = C; the wave's share of dW is one 16-row tile -- at C = 32 the four waves take the four 16 x 16 tiles of the [32][32] output)
+//   FAN  a second consumer's gradient dy2 (norm1's patch-major output feeding the spatial-reduction convolution: rows in patch_row order when
+//        lw >= 0) is added to the bf16-rounded dy on load, in fp32, exactly as ln_bwd_kernel adds its dy2.
+template <int KS, int HM = 4> struct LnlGeom {
+    static constexpr int C = 32 * KS, H = HM * C;
     static constexpr int RD = 2 * H + 16, RY = 2 * C + 16;               // staged row bytes (+16: bank spread)
-    static constexpr int NFRAG = 8 * KS * KS;                            // W1 fragments of 1 KB: [2 KS feature tiles][4 KS k-steps]
-    static constexpr int OFF_Y = 64 * RD, OFF_W = OFF_Y + 64 * RY, OFF_G = OFF_W + 1024 * NFRAG, LDS_BYTES = OFF_G + 4 * C;
+    static constexpr int KSTEPS = H / 32;
+    static constexpr int NFRAG = 2 * KS * KSTEPS;                        // W1 fragments of 1 KB: [2 KS feature tiles][H / 32 k-steps]
+    static constexpr int OFF_Y = 64 * RD, OFF_W = OFF_Y + 64 * RY, OFF_G = OFF_W + 1024 * NFRAG, LDS_BYTES = OFF_G + 8 * C;   // gamma | beta
 };
-template <int KS>
-__global__ void __launch_bounds__(256, 2) ln_linear_bwd_kernel(const bf16_t* __restrict__ dh, const bf16_t* __restrict__ w1 /*[4C][C]*/,
+__device__ __forceinline__ void lnl_chunk_y(const float (&xh)[8], const float (&g)[8], const float (&b)[8], float (&o)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = __builtin_fmaf(g[j], xh[j], b[j]);
+}
+template <int KS, bool YX = false, int HM = 4, bool FAN = false>
+__global__ void __launch_bounds__(256, 2) ln_linear_bwd_kernel(const bf16_t* __restrict__ dh, const bf16_t* __restrict__ w1 /*[H][C]*/,
                                                                 const bf16_t* __restrict__ x, const bf16_t* __restrict__ y,
                                                                 const bf16_t* __restrict__ dres /*nullable*/, const float* __restrict__ gamma,
                                                                 const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                 bf16_t* __restrict__ dx, const float* __restrict__ rsc /*nullable*/, uint32_t rpg,
                                                                 bf16_t* __restrict__ dxs, bf16_t* __restrict__ dyo /*nullable: the fc1 data gradient*/,
-                                                                float* __restrict__ pw /*[grid][4C][C]*/, float* __restrict__ pb /*[grid][4C]*/,
+                                                                float* __restrict__ pw /*[grid][H][C]*/, float* __restrict__ pb /*[grid][H]*/,
                                                                 float* __restrict__ pg /*[grid][2][C]*/, int64_t rows,
-                                                                int ksplit /*C = 64: K-quarter partials (else one chain over K)*/) {
-    typedef LnlGeom<KS> G;
-    constexpr int C = G::C, H = G::H, RD = G::RD, RY = G::RY;
+                                                                int ksplit /*C = 64: K-quarter partials (else one chain over K)*/,
+                                                                const float* __restrict__ beta /*YX*/, const bf16_t* __restrict__ dy2 /*FAN*/, int lw, int ls) {
+    typedef LnlGeom<KS, HM> G;
+    constexpr int C = G::C, H = G::H, RD = G::RD, RY = G::RY, KSTEPS = G::KSTEPS;
     constexpr int NT = 2 * KS;                                           // 16-feature tiles of dy
-    constexpr int NQ = KS == 1 ? 1 : 4, SPQ = KS == 1 ? 4 : 2;           // accumulation chains over K and 32-steps per chain
+    constexpr int NQ = (KS == 1 || HM == 1) ? 1 : 4, SPQ = HM == 1 ? KS : (KS == 1 ? 4 : 2);           // accumulation chains over K and 32-steps per chain
     constexpr int ND = H / 32, NY = KS;                                  // 16-byte chunks per thread of a staged dh / y tile
+    constexpr bool QUAD = HM == 1 && KS == 1;                            // H / 4 = 8 rows per wave would split a tile: wave -> (row tile, column tile)
+    constexpr int NI = HM == 1 ? 1 : NT, NJ = QUAD ? 1 : NT;             // the wave's block of dW1 in 16 x 16 tiles
     extern __shared__ __attribute__((aligned(16))) unsigned char lnl_lds[];
     unsigned char* dhs = lnl_lds;
     unsigned char* ys = lnl_lds + G::OFF_Y;
@@ -461,7 +480,7 @@ __global__ void __launch_bounds__(256, 2) ln_linear_bwd_kernel(const bf16_t* __r
     // W1 fragments in LDS, fragment (nt, ks) at 1 KB * (nt * 4 KS + ks): MFMA row i of tile nt carries feature
     // 32 (nt >> 1) + 8 (i >> 2) + 4 (nt & 1) + (i & 3) and lane group g the k rows 32 ks + 8 g .. + 7 (gemm_skinny_kernel, LAYOUT 1)
     for (int f = wave; f < G::NFRAG; f += 4) {
-        const int nt = f / (4 * KS), ks = f - nt * (4 * KS);
+        const int nt = f / KSTEPS, ks = f - nt * KSTEPS;
         const int n = 32 * (nt >> 1) + 8 * (mi >> 2) + 4 * (nt & 1) + (mi & 3);
         lnl_s16x8 w;
 #pragma unroll
@@ -470,16 +489,19 @@ __global__ void __launch_bounds__(256, 2) ln_linear_bwd_kernel(const bf16_t* __r
     }
     float* gml = reinterpret_cast<float*>(lnl_lds + G::OFF_G);           // gamma, read back per tile (16 registers fewer at C = 64)
     if (tid < C) gml[tid] = gamma[tid];
+    float* btl = gml + C;
+    if (YX && tid < C) btl[tid] = beta[tid];
+    const int rowbase = QUAD ? 16 * (wave >> 1) : (H / 4) * wave, jbase = QUAD ? (wave & 1) : 0;
     // dgamma / dbeta: a token's 16 lanes (one DPP row) sum each of the lane group's 8 KS features per tile, and lane mi keeps
     // the running sum of feature 32 (mi >> 3) + 8 g + (mi & 7) -- two accumulators per lane instead of 16 KS
     float accg = 0.f, accb = 0.f;
     // this wave's [H / 4 x C] block of dW1; its db1 rows share ONE accumulator tile: row tile i is multiplied by a B fragment
     // whose column i is all ones, so column i of the tile collects colsum(dh) of rows 16 i .. 16 i + 15
-    lnl_f32x4 aw[NT][NT], ab = lnl_f32x4{0.f, 0.f, 0.f, 0.f};
+    lnl_f32x4 aw[NI][NJ], ab = lnl_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int i = 0; i < NT; ++i)
+    for (int i = 0; i < NI; ++i)
 #pragma unroll
-        for (int j = 0; j < NT; ++j) aw[i][j] = lnl_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < NJ; ++j) aw[i][j] = lnl_f32x4{0.f, 0.f, 0.f, 0.f};
     float bz = 0.f;                                                      // the absent bias of the data-gradient product (acc + 0, as that kernel adds it)
     asm volatile("" : "+v"(bz));
     const float invC = 1.f / (float)C;
@@ -503,10 +525,12 @@ __global__ void __launch_bounds__(256, 2) ln_linear_bwd_kernel(const bf16_t* __r
             const int lr = drow + RPD * i < last ? drow + RPD * i : last;
             rd[i] = *reinterpret_cast<const lnl_u32x4*>(dht + (uint32_t)(lr * H + dcol));
         }
+        if (!YX) {
 #pragma unroll
-        for (int i = 0; i < NY; ++i) {
-            const int lr = yrow + RPY * i < last ? yrow + RPY * i : last;
-            ry[i] = *reinterpret_cast<const lnl_u32x4*>(yt + (uint32_t)(lr * C + ycol));
+            for (int i = 0; i < NY; ++i) {
+                const int lr = yrow + RPY * i < last ? yrow + RPY * i : last;
+                ry[i] = *reinterpret_cast<const lnl_u32x4*>(yt + (uint32_t)(lr * C + ycol));
+            }
         }
     };
     int64_t tile = blockIdx.x;
@@ -518,8 +542,10 @@ __global__ void __launch_bounds__(256, 2) ln_linear_bwd_kernel(const bf16_t* __r
         const int last = tile_last(tile);
 #pragma unroll
         for (int i = 0; i < ND; ++i) *reinterpret_cast<lnl_u32x4*>(dst_d + RPD * i * RD) = drow + RPD * i <= last ? rd[i] : zero4;
+        if (!YX) {
 #pragma unroll
-        for (int i = 0; i < NY; ++i) *reinterpret_cast<lnl_u32x4*>(dst_y + RPY * i * RY) = yrow + RPY * i <= last ? ry[i] : zero4;
+            for (int i = 0; i < NY; ++i) *reinterpret_cast<lnl_u32x4*>(dst_y + RPY * i * RY) = yrow + RPY * i <= last ? ry[i] : zero4;
+        }
         // this tile's LayerNorm operands of the lane's token
         const int lrow = 16 * wave + mi;
         const bool rv = lrow <= last;
@@ -527,11 +553,14 @@ __global__ void __launch_bounds__(256, 2) ln_linear_bwd_kernel(const bf16_t* __r
         const uint32_t eo = (uint32_t)(lrc * C + 8 * g);                 // the lane's first chunk, elements from the tile's first row
         const bf16_t* xt = x + r0 * C;
         const bf16_t* rt = dres + r0 * C;
-        lnl_u32x4 rx[KS], rr[KS];
+        lnl_u32x4 rx[KS], rr[KS], r2[KS];
+        const bf16_t* d2t = nullptr;
+        if (FAN) d2t = lw >= 0 ? dy2 + patch_row(r0 + lrc, lw, ls) * C + 8 * g : dy2 + r0 * C + eo;
 #pragma unroll
         for (int q = 0; q < KS; ++q) {
             rx[q] = *reinterpret_cast<const lnl_u32x4*>(xt + (eo + 32 * q));
             if (dres) rr[q] = *reinterpret_cast<const lnl_u32x4*>(rt + (eo + 32 * q));
+            if (FAN) r2[q] = *reinterpret_cast<const lnl_u32x4*>(d2t + 32 * q);
         }
         const float mu = (mean + r0)[lrc], rs = rv ? (rstd + r0)[lrc] : 0.f;
         float sc = 0.f;
@@ -561,7 +590,7 @@ __global__ void __launch_bounds__(256, 2) ln_linear_bwd_kernel(const bf16_t* __r
                     if (kq != 0 && !ksplit) a = sum[nt];                 // one chain over all of K
 #pragma unroll
                     for (int s = 0; s < SPQ; ++s) {
-                        const lnl_bf16x8 wf = *reinterpret_cast<const lnl_bf16x8*>(wl + 1024 * (nt * 4 * KS + kq * SPQ + s) + 16 * lane);
+                        const lnl_bf16x8 wf = *reinterpret_cast<const lnl_bf16x8*>(wl + 1024 * (nt * KSTEPS + kq * SPQ + s) + 16 * lane);
                         a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xa[s], a, 0, 0, 0);
                     }
                     if (kq == 0 || !ksplit) sum[nt] = a; else sum[nt] = sum[nt] + a;
@@ -585,8 +614,22 @@ __global__ void __launch_bounds__(256, 2) ln_linear_bwd_kernel(const bf16_t* __r
                 float xv[8], dv[8], gm[8], xh[8];
                 lnl_unpack8(rx[q], xv);
                 lnl_unpack8(dp[q], dv);
+                if (FAN) {
+                    if (!rv) r2[q] = lnl_u32x4{0u, 0u, 0u, 0u};
+                    float d2[8];
+                    lnl_unpack8(r2[q], d2);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) dv[j] = dv[j] + d2[j];
+                }
                 load8f(gml + 32 * q + 8 * g, gm);
                 lnl_chunk_sums(xv, dv, gm, mu, rs, xh, s1[q], s2[q]);
+                if (YX) {
+                    // the lane's chunk of y into the staged tile (zero rows past the end, as the staging of a stored y leaves them)
+                    float bt[8], yv[8];
+                    load8f(btl + 32 * q + 8 * g, bt);
+                    lnl_chunk_y(xh, gm, bt, yv);
+                    *reinterpret_cast<lnl_u32x4*>(ys + lrow * RY + 2 * (32 * q + 8 * g)) = rv ? lnl_pack8(yv) : lnl_u32x4{0u, 0u, 0u, 0u};
+                }
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const float ag = wave_sum(dv[j] * xh[j], 16), abt = wave_sum(dv[j], 16);
@@ -604,6 +647,12 @@ __global__ void __launch_bounds__(256, 2) ln_linear_bwd_kernel(const bf16_t* __r
                 float xv[8], dv[8], gm[8], o[8], res[8];
                 lnl_unpack8(rx[q], xv);
                 lnl_unpack8(dp[q], dv);
+                if (FAN) {
+                    float d2[8];
+                    lnl_unpack8(r2[q], d2);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) dv[j] = dv[j] + d2[j];
+                }
                 load8f(gml + 32 * q + 8 * g, gm);
                 if (dres) lnl_unpack8(rr[q], res);
                 else {
@@ -624,24 +673,25 @@ __global__ void __launch_bounds__(256, 2) ln_linear_bwd_kernel(const bf16_t* __r
             }
         }
         if (KS != 1) load_tile(nxt);
+        if (YX) __syncthreads();                                         // the four waves' rows of y are staged
         __builtin_amdgcn_sched_barrier(0);
         // ---- dW1 += dh^T y, db1 += colsum(dh): rows [H / 4 wave, + H / 4) over the tile's 64 tokens (two k-steps of 32)
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-            lnl_bf16x8 fa[NT];
+            lnl_bf16x8 fa[NI];
 #pragma unroll
-            for (int i = 0; i < NT; ++i) {
-                fa[i] = lnl_frag_tok_tr(dhs + kk * 32 * RD, RD, (H / 4) * wave + 16 * i, lane);
+            for (int i = 0; i < NI; ++i) {
+                fa[i] = lnl_frag_tok_tr(dhs + kk * 32 * RD, RD, rowbase + 16 * i, lane);
                 uint32_t one2 = mi == i ? 0x3f803f80u : 0u;
                 asm volatile("" : "+v"(one2));                           // (built here: kept across the loop the four selectors are 16 registers)
                 const lnl_u32x4 sel = {one2, one2, one2, one2};
                 ab = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], __builtin_bit_cast(lnl_bf16x8, sel), ab, 0, 0, 0);
             }
 #pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                const lnl_bf16x8 fb = lnl_frag_tok_tr(ys + kk * 32 * RY, RY, 16 * j, lane);
+            for (int j = 0; j < NJ; ++j) {
+                const lnl_bf16x8 fb = lnl_frag_tok_tr(ys + kk * 32 * RY, RY, 16 * (jbase + j), lane);
 #pragma unroll
-                for (int i = 0; i < NT; ++i) aw[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, aw[i][j], 0, 0, 0);
+                for (int i = 0; i < NI; ++i) aw[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, aw[i][j], 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -650,17 +700,17 @@ __global__ void __launch_bounds__(256, 2) ln_linear_bwd_kernel(const bf16_t* __r
     float* pwb = pw + (int64_t)blockIdx.x * H * C;
     float* pbb = pb + (int64_t)blockIdx.x * H;
 #pragma unroll
-    for (int i = 0; i < NT; ++i) {
+    for (int i = 0; i < NI; ++i) {
 #pragma unroll
         for (int rr_ = 0; rr_ < 4; ++rr_) {
-            const int m = (H / 4) * wave + 16 * i + 4 * g + rr_;
+            const int m = rowbase + 16 * i + 4 * g + rr_;
 #pragma unroll
-            for (int j = 0; j < NT; ++j) pwb[m * C + 16 * j + mi] = aw[i][j][rr_];
+            for (int j = 0; j < NJ; ++j) pwb[m * C + 16 * (jbase + j) + mi] = aw[i][j][rr_];
         }
     }
-    if (mi < NT) {
+    if (mi < NI && jbase == 0) {                                         // (QUAD: the two waves of a row tile hold the same column sums)
 #pragma unroll
-        for (int rr_ = 0; rr_ < 4; ++rr_) pbb[(H / 4) * wave + 16 * mi + 4 * g + rr_] = ab[rr_];
+        for (int rr_ = 0; rr_ < 4; ++rr_) pbb[rowbase + 16 * mi + 4 * g + rr_] = ab[rr_];
     }
     // dgamma / dbeta: across the waves through LDS in fixed order
     __syncthreads();
@@ -690,16 +740,27 @@ extern "C" int segf_layernorm_linear_bwd_blocks(int64_t rows) { return rows > 0 
 extern "C" int64_t segf_layernorm_linear_bwd_ws(int64_t rows, int C, int N) {
     return rows > 0 ? (int64_t)lnl_blocks(rows) * ((int64_t)N * C + N + 2 * C) : 0;
 }
-extern "C" int segf_layernorm_linear_bwd(int dt, int64_t rows, int C, int N, const void* dh, const void* w1, const void* x, const void* y,
-                                         const void* dres, const float* gamma, const float* mean, const float* rstd, void* dx,
-                                         const float* rscale, int64_t rows_per_group, void* dxs, void* dy_out, float* dw1, float* db1,
-                                         float* dgamma, float* dbeta, float* ws, void* stream) {
+// The general entry point: N = 4 C or N = C, y nullable (NULL: rebuilt from x, mean, rstd, gamma and beta -- the forward then keeps no y),
+// dy2 nullable (a second consumer's gradient of the LayerNorm output, in patch-major row order when log2_w >= 0, in token order otherwise).
+extern "C" int segf_layernorm_linear_bwd_ex_supported(int dt, int64_t rows, int C, int N) {
+    const int pol = POL(ln_linear_bwd_fused);
+    if (pol <= 0 || dt != SEGF_BF16 || (C != 32 && C != 64) || (N != 4 * C && N != C)) return 0;
+    if (rows <= 0 || rows > 0x7fffffffll) return 0;
+    return (pol >= 2 || rows >= 131072) ? 1 : 0;
+}
+extern "C" int segf_layernorm_linear_bwd_ex(int dt, int64_t rows, int C, int N, const void* dh, const void* w1, const void* x, const void* y,
+                                            const float* beta, const void* dy2, int log2_w, int log2_sr, const void* dres, const float* gamma,
+                                            const float* mean, const float* rstd, void* dx, const float* rscale, int64_t rows_per_group, void* dxs,
+                                            void* dy_out, float* dw1, float* db1, float* dgamma, float* dbeta, float* ws, void* stream) {
     if (dt != SEGF_BF16) return SEGF_ERR_DTYPE;
-    if ((C != 32 && C != 64) || N != 4 * C || rows <= 0 || rows > 0x7fffffffll) return SEGF_ERR_SHAPE;
+    if ((C != 32 && C != 64) || (N != 4 * C && N != C) || rows <= 0 || rows > 0x7fffffffll) return SEGF_ERR_SHAPE;
+    if (y ? N != 4 * C : !beta) return SEGF_ERR_SHAPE;                   // a stored y: the norm2 -> fc1 form only
+    if (dy2 && N != C) return SEGF_ERR_SHAPE;                            // the fan-in: norm1 -> q only (at C = 64 the hidden-width form has no registers for it)
+    if (dy2 && log2_w >= 0 && !patch_geom_ok(rows, log2_w, log2_sr)) return SEGF_ERR_SHAPE;
     if ((rscale != nullptr) != (dxs != nullptr)) return SEGF_ERR_SHAPE;
     if (rscale && (rows_per_group <= 0 || rows_per_group > 0x7fffffffll)) return SEGF_ERR_SHAPE;
-    if (((uintptr_t)dh % 16) || ((uintptr_t)w1 % 2) || ((uintptr_t)x % 16) || ((uintptr_t)y % 16) || ((uintptr_t)dres % 16) ||
-        ((uintptr_t)gamma % 16) || ((uintptr_t)dx % 16) || ((uintptr_t)dxs % 16) || ((uintptr_t)dy_out % 16)) return SEGF_ERR_SHAPE;
+    if (((uintptr_t)dh % 16) || ((uintptr_t)w1 % 2) || ((uintptr_t)x % 16) || ((uintptr_t)y % 16) || ((uintptr_t)dres % 16) || ((uintptr_t)dy2 % 16) ||
+        ((uintptr_t)gamma % 16) || ((uintptr_t)beta % 16) || ((uintptr_t)dx % 16) || ((uintptr_t)dxs % 16) || ((uintptr_t)dy_out % 16)) return SEGF_ERR_SHAPE;
     if (!ws) return SEGF_ERR_WORKSPACE;
     const bool now = dw1 != nullptr;                                     // NULL: deferred finalize (segf_colreduce_finalize_grouped on the three partial blocks)
     if (now ? (!db1 || !dgamma || dbeta != dgamma + C) : (db1 || dgamma || dbeta)) return SEGF_ERR_SHAPE;
@@ -710,20 +771,31 @@ extern "C" int segf_layernorm_linear_bwd(int dt, int64_t rows, int C, int N, con
     float* pg = pb + (int64_t)blocks * N;
     const uint32_t rpg = rscale ? (uint32_t)rows_per_group : 1u;
     // the order in which segf_gemm (layout 1) sums K = 256 at this row count: gemm_skinny_k_kernel's quarters from 65536 rows on
-    // (gemm.hip: gemm_skinny_k_ok), one chain on the 128-tile kernel below
-    const int ksplit = C == 64 && rows >= 65536 && !POL(gemm_no_skinny_k) && !POL(gemm_no_skinny);
+    // (gemm.hip: gemm_skinny_k_ok), one chain on the 128-tile kernel below.  K = C <= 64 (N == C) is one chain at every row count.
+    const int ksplit = N == 4 * C && C == 64 && rows >= 65536 && !POL(gemm_no_skinny_k) && !POL(gemm_no_skinny);
+    const int lw = dy2 ? log2_w : -1;
     // C = 64 stages 75 KB: above the 64 KB a kernel gets by default, so the limit is raised on the function, once per device
-#define LNL(KS_) do { \
+#define LNL_GO(LDSB, ...) do { \
         static int lds_dev = -1; \
         int dev = -1; \
-        if (LnlGeom<KS_>::LDS_BYTES > 65536 && !segf_trace().dry && hipGetDevice(&dev) == hipSuccess && dev != lds_dev) { \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ln_linear_bwd_kernel<KS_>), hipFuncAttributeMaxDynamicSharedMemorySize, LnlGeom<KS_>::LDS_BYTES) != hipSuccess) return SEGF_ERR_SHAPE; \
+        if (LDSB > 65536 && !segf_trace().dry && hipGetDevice(&dev) == hipSuccess && dev != lds_dev) { \
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&__VA_ARGS__), hipFuncAttributeMaxDynamicSharedMemorySize, LDSB) != hipSuccess) return SEGF_ERR_SHAPE; \
             lds_dev = dev; \
         } \
-        hipLaunchKernelGGL((ln_linear_bwd_kernel<KS_>), dim3(blocks), dim3(256), LnlGeom<KS_>::LDS_BYTES, st, (const bf16_t*)dh, (const bf16_t*)w1, (const bf16_t*)x, \
-                           (const bf16_t*)y, (const bf16_t*)dres, gamma, mean, rstd, (bf16_t*)dx, rscale, rpg, (bf16_t*)dxs, (bf16_t*)dy_out, pw, pb, pg, rows, ksplit); } while (0)
-    if (C == 32) LNL(1); else LNL(2);
+        hipLaunchKernelGGL((__VA_ARGS__), dim3(blocks), dim3(256), LDSB, st, (const bf16_t*)dh, (const bf16_t*)w1, (const bf16_t*)x, \
+                           (const bf16_t*)y, (const bf16_t*)dres, gamma, mean, rstd, (bf16_t*)dx, rscale, rpg, (bf16_t*)dxs, (bf16_t*)dy_out, pw, pb, pg, rows, ksplit, \
+                           beta, (const bf16_t*)dy2, lw, log2_sr); } while (0)
+#define LNL(KS_) LNL_GO((LnlGeom<KS_>::LDS_BYTES), ln_linear_bwd_kernel<KS_>)
+#define LNLX(KS_, HM_, FAN_) LNL_GO((LnlGeom<KS_, HM_>::LDS_BYTES), ln_linear_bwd_kernel<KS_, true, HM_, FAN_>)
+    if (y) { if (C == 32) LNL(1); else LNL(2); }
+    else if (N == 4 * C) { if (C == 32) LNLX(1, 4, false); else LNLX(2, 4, false); }
+    else {
+        if (dy2) { if (C == 32) LNLX(1, 1, true); else LNLX(2, 1, true); }
+        else { if (C == 32) LNLX(1, 1, false); else LNLX(2, 1, false); }
+    }
+#undef LNLX
 #undef LNL
+#undef LNL_GO
     SEGF_CHECK_LAUNCH();
     if (!now) return 0;
     colreduce_finalize_launch(pw, blocks, (int64_t)N * C, dw1, st);
@@ -731,6 +803,264 @@ extern "C" int segf_layernorm_linear_bwd(int dt, int64_t rows, int C, int N, con
     colreduce_finalize_launch(pb, blocks, N, db1, st);
     SEGF_CHECK_LAUNCH();
     colreduce_finalize_launch(pg, blocks, 2 * (int64_t)C, dgamma, st);
+    SEGF_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int segf_layernorm_linear_bwd(int dt, int64_t rows, int C, int N, const void* dh, const void* w1, const void* x, const void* y,
+                                         const void* dres, const float* gamma, const float* mean, const float* rstd, void* dx,
+                                         const float* rscale, int64_t rows_per_group, void* dxs, void* dy_out, float* dw1, float* db1,
+                                         float* dgamma, float* dbeta, float* ws, void* stream) {
+    if (dt != SEGF_BF16) return SEGF_ERR_DTYPE;
+    if (N != 4 * C || !y) return SEGF_ERR_SHAPE;
+    return segf_layernorm_linear_bwd_ex(dt, rows, C, N, dh, w1, x, y, nullptr, nullptr, -1, 0, dres, gamma, mean, rstd, dx, rscale, rows_per_group, dxs,
+                                        dy_out, dw1, db1, dgamma, dbeta, ws, stream);
+}
+
+// ---- LayerNorm as the operand prologue of the streaming thin product -------------------------------------------------------------
+// `norm2 -> mlp.fc1` and `norm1 -> attn.q` of a MiT block (mit.py:45,98,136-146) at C = 32 / 64 as two launches write the C-wide LayerNorm
+// output and read it back only to feed a product with K = C.  Here gemm_skinny_kernel's structure (gemm.hip, layout 0:
+// weight fragments resident, a wave walks 16-token groups, the token rows ARE the MFMA B operand as they lie, the next group's rows in flight)
+// takes the rows of x instead: lane (mi, g) holds features 32 s + 8 g .. + 7 of token mi, normalises them in registers and the bf16-rounded
+// result is the B operand.  A token's chunks sit 16 lanes apart; the row sums pair them as ln_fwd_kernel's wave_sum(., lpr) does
+// (xor 1, xor 2 on the chunk index = lanes 16 and 32 apart; at C = 64 then xor 4 = the lane's own second chunk).  The arithmetic is
+// ln_fwd_kernel's as its gfx950 code performs it -- chunk sums from 0 in element order, mean = sum * (1 / C), squares of the differences as
+// rounded products summed in element order, rstd = rsqrt(fma(sum, 1 / C, eps)), y = fma(gamma, (x - mean) * rstd, beta) -- with contraction
+// off and the fused operations spelled out, so that mean, rstd and the rounded y carry that kernel's bits whatever the optimiser would choose
+// here.  The product is gemm_skinny_kernel's chain (zero accumulator, K steps ascending, + bias, one rounding).  N = 16 NT NCH: NCH > 1
+// (C = 64 -> 256: 32 fragments) keeps the fragments in LDS and loops the column chunks over the rows already normalised.
+// Optional outputs: y in token order (HASY) and in patch-major row order (HASY2: segf_layernorm_fwd_patch's y2).
+__device__ __forceinline__ float lnf_sum8(const float (&v)[8]) {
+#pragma clang fp contract(off)
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s = s + v[j];
+    return s;
+}
+__device__ __forceinline__ float lnf_sq8(const float (&v)[8], float mu) {
+#pragma clang fp contract(off)
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { const float d = v[j] - mu; const float dd = d * d; q = q + dd; }
+    return q;
+}
+__device__ __forceinline__ float lnf_mean(float s, float invC) {
+#pragma clang fp contract(off)
+    return s * invC;
+}
+__device__ __forceinline__ float lnf_rstd(float q, float invC, float eps) {
+#pragma clang fp contract(off)
+    return rsqrtf(__builtin_fmaf(q, invC, eps));
+}
+__device__ __forceinline__ void lnf_y8(const float (&v)[8], const float (&g)[8], const float (&b)[8], float mu, float rs, float (&o)[8]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { const float t = (v[j] - mu) * rs; o[j] = __builtin_fmaf(g[j], t, b[j]); }
+}
+template <int KS, int NT, int NCH, bool HASY, bool HASY2>
+__global__ void __launch_bounds__(256) ln_linear_fwd_kernel(const bf16_t* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                             const bf16_t* __restrict__ w /*[N][C]*/, const float* __restrict__ bias,
+                                                             bf16_t* __restrict__ out /*[rows][N]*/, float* __restrict__ mean_out,
+                                                             float* __restrict__ rstd_out, bf16_t* __restrict__ y, bf16_t* __restrict__ y2,
+                                                             int64_t rows, float eps, int lw, int ls) {
+    constexpr int C = 32 * KS, N = 16 * NT * NCH;
+    constexpr bool WREG = NCH == 1;                                     // NT * KS <= 16 fragments: register-resident
+    static_assert(!WREG || NT * KS <= 16, "fragment budget");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int mi = lane & 15, g = lane >> 4;
+    constexpr int SROW = 32 * NT + 16;                                  // staged output row bytes (+16: bank spread)
+    __shared__ __attribute__((aligned(16))) unsigned char ostage[4][16 * SROW];
+    __shared__ __attribute__((aligned(16))) unsigned char wl[WREG ? 16 : 1024 * NT * KS * NCH];
+    __shared__ __attribute__((aligned(16))) float bl[WREG ? 4 : N];
+    unsigned char* ost = ostage[wave];
+    // weight fragments: MFMA row i of tile nt carries feature n0 + 32 (nt >> 1) + 8 (i >> 2) + 4 (nt & 1) + (i & 3) (gemm_skinny_kernel)
+    lnl_bf16x8 Wf[WREG ? NT : 1][KS];
+    float bv[WREG ? NT : 1][4];
+    if (WREG) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int n = 32 * (nt >> 1) + 8 * (mi >> 2) + 4 * (nt & 1) + (mi & 3);
+#pragma unroll
+            for (int s = 0; s < KS; ++s) Wf[nt][s] = __builtin_bit_cast(lnl_bf16x8, *reinterpret_cast<const lnl_u32x4*>(w + n * C + 32 * s + 8 * g));
+#pragma unroll
+            for (int r = 0; r < 4; ++r) bv[nt][r] = bias[32 * (nt >> 1) + 8 * g + 4 * (nt & 1) + r];
+        }
+    } else {
+        for (int f = wave; f < NT * KS * NCH; f += 4) {                 // fragment (ch, nt, s) at 1 KB * ((ch NT + nt) KS + s)
+            const int s = f % KS, cn = f / KS, ch = cn / NT, nt = cn - ch * NT;
+            const int n = 16 * NT * ch + 32 * (nt >> 1) + 8 * (mi >> 2) + 4 * (nt & 1) + (mi & 3);
+            *reinterpret_cast<lnl_u32x4*>(wl + 1024 * f + 16 * lane) = *reinterpret_cast<const lnl_u32x4*>(w + n * C + 32 * s + 8 * g);
+        }
+        for (int i = threadIdx.x; i < N; i += 256) bl[i] = bias[i];
+        __syncthreads();
+    }
+    float gm[KS][8], bt[KS][8];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) { load8f(gamma + 32 * s + 8 * g, gm[s]); load8f(beta + 32 * s + 8 * g, bt[s]); }
+    const float invC = 1.f / (float)C;
+    const int64_t ngroups = (rows + 15) / 16, gstride = (int64_t)gridDim.x * 4;
+    int64_t grp = (int64_t)blockIdx.x * 4 + wave;
+    lnl_u32x4 xa[KS], xb[KS];
+    auto rowptr = [&](int64_t gp) {
+        int64_t m = gp * 16 + mi;
+        m = m < rows ? m : rows - 1;
+        return x + m * C + 8 * g;
+    };
+    {
+        const bf16_t* p = rowptr(grp < ngroups ? grp : 0);
+#pragma unroll
+        for (int s = 0; s < KS; ++s) xa[s] = *reinterpret_cast<const lnl_u32x4*>(p + 32 * s);
+    }
+    // One group of 16 tokens; FULL = every row exists (all loads and stores of the main loop unconditional, as in gemm_skinny_kernel)
+    auto one_group = [&](int64_t gp, auto full_tag) {
+        constexpr bool FULL = decltype(full_tag)::value;
+        {
+            const int64_t nxt = gp + gstride;
+            const bf16_t* p = rowptr(nxt < ngroups ? nxt : gp);           // unconditional (the last one re-reads)
+#pragma unroll
+            for (int s = 0; s < KS; ++s) xb[s] = *reinterpret_cast<const lnl_u32x4*>(p + 32 * s);
+            SEGF_LOADS_ISSUED();
+        }
+        const int64_t m = gp * 16 + mi;
+        const bool mok = FULL || m < rows;
+        // ---- LayerNorm of the lane's token
+        float v[KS][8], ps[KS], pq[KS];
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            lnl_unpack8(xa[s], v[s]);
+            ps[s] = lnf_sum8(v[s]);
+            ps[s] += __shfl_xor(ps[s], 16, 64); ps[s] += __shfl_xor(ps[s], 32, 64);
+        }
+        float tot = ps[0];
+        if (KS == 2) tot += ps[KS - 1];
+        const float mu = lnf_mean(tot, invC);
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            pq[s] = lnf_sq8(v[s], mu);
+            pq[s] += __shfl_xor(pq[s], 16, 64); pq[s] += __shfl_xor(pq[s], 32, 64);
+        }
+        float qt = pq[0];
+        if (KS == 2) qt += pq[KS - 1];
+        const float rs = lnf_rstd(qt, invC, eps);
+        lnl_u32x4 yb[KS];
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            float o[8];
+            lnf_y8(v[s], gm[s], bt[s], mu, rs, o);
+            yb[s] = lnl_pack8(o);
+        }
+        if (mok) {
+            if (g == 0) { mean_out[m] = mu; rstd_out[m] = rs; }
+            if (HASY) {
+#pragma unroll
+                for (int s = 0; s < KS; ++s) *reinterpret_cast<lnl_u32x4*>(y + m * C + 32 * s + 8 * g) = yb[s];
+            }
+            if (HASY2) {
+                bf16_t* p2 = y2 + patch_row(m, lw, ls) * C + 8 * g;
+#pragma unroll
+                for (int s = 0; s < KS; ++s) *reinterpret_cast<lnl_u32x4*>(p2 + 32 * s) = yb[s];
+            }
+        }
+        // ---- the product, a column chunk of 16 NT features at a time
+#pragma unroll 1
+        for (int ch = 0; ch < NCH; ++ch) {
+            lnl_f32x4 acc[NT];
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                acc[nt] = lnl_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    lnl_bf16x8 wf;
+                    if (WREG) wf = Wf[nt][s];
+                    else wf = *reinterpret_cast<const lnl_bf16x8*>(wl + 1024 * ((ch * NT + nt) * KS + s) + 16 * lane);
+                    acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, __builtin_bit_cast(lnl_bf16x8, yb[s]), acc[nt], 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < NT / 2; ++q) {
+                float b0[4], b1[4], o[8];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    b0[r] = WREG ? bv[2 * q][r] : bl[16 * NT * ch + 32 * q + 8 * g + r];
+                    b1[r] = WREG ? bv[2 * q + 1][r] : bl[16 * NT * ch + 32 * q + 8 * g + 4 + r];
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { o[r] = acc[2 * q][r] + b0[r]; o[4 + r] = acc[2 * q + 1][r] + b1[r]; }
+                *reinterpret_cast<lnl_u32x4*>(ost + mi * SROW + (32 * q + 8 * g) * 2) = lnl_pack8(o);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            {
+                constexpr int CPR = 2 * NT;                              // 16-byte chunks per staged row
+#pragma unroll
+                for (int i = 0; i < (16 * CPR) / 64; ++i) {
+                    const int idx = lane + 64 * i, row = idx / CPR, cc = idx - row * CPR;
+                    const lnl_u32x4 o = *reinterpret_cast<const lnl_u32x4*>(ost + row * SROW + 16 * cc);
+                    const int64_t mr = gp * 16 + row;
+                    if (FULL || mr < rows) *reinterpret_cast<lnl_u32x4*>(out + mr * N + 16 * NT * ch + 8 * cc) = o;
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            xa[s] = xb[s];
+            asm volatile("" : "+v"(xa[s]));       // keep the copy (and its counted wait) here, behind this group's stores
+        }
+    };
+    const int64_t nfull = rows / 16;                                      // groups whose 16 rows all exist
+    // everything loaded so far is consumed here once (gemm_skinny_kernel: otherwise the loop header waits for the previous group's stores)
+    if (WREG) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+#pragma unroll
+            for (int s2 = 0; s2 < KS; ++s2) asm volatile("" : "+v"(Wf[nt][s2]));
+#pragma unroll
+            for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(bv[nt][r]));
+        }
+    }
+#pragma unroll
+    for (int s2 = 0; s2 < KS; ++s2) {
+        asm volatile("" : "+v"(xa[s2]));
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { asm volatile("" : "+v"(gm[s2][j])); asm volatile("" : "+v"(bt[s2][j])); }
+    }
+    for (; grp < nfull; grp += gstride) one_group(grp, std::true_type{});
+    if (grp < ngroups) one_group(grp, std::false_type{});                 // at most one ragged group, in one wave
+}
+
+static inline int lnf_blocks(int64_t rows) { return (int)imin64(cdiv64(cdiv64(rows, 16), 4 * 4), 2048); }     // >= 4 token groups per wave, as the product it replaces
+// The shapes the fused forward exists for and the sizes the policy sends to it (SEGFAC_LN_LINEAR_FWD_FUSED: 0 never, 1 from 131072 token
+// rows on -- the recorded batch-4 step keeps its two launches --, 2 wherever the shape has the kernel)
+extern "C" int segf_layernorm_linear_fwd_supported(int dt, int64_t rows, int C, int N) {
+    const int pol = POL(ln_linear_fwd_fused);
+    if (pol <= 0 || dt != SEGF_BF16 || (C != 32 && C != 64) || (N != C && N != 4 * C)) return 0;
+    if (rows <= 0 || rows > 0x7fffffffll) return 0;
+    return (pol >= 2 || rows >= 131072) ? 1 : 0;
+}
+extern "C" int segf_layernorm_linear_fwd_blocks(int64_t rows) { return rows > 0 ? lnf_blocks(rows) : 0; }
+extern "C" int segf_layernorm_linear_fwd(int dt, int64_t rows, int C, int N, const void* x, const float* gamma, const float* beta, float eps,
+                                         const void* w, const float* bias, void* out, float* mean, float* rstd, void* y, void* y2, int log2_w,
+                                         int log2_sr, void* stream) {
+    if (dt != SEGF_BF16) return SEGF_ERR_DTYPE;
+    if ((C != 32 && C != 64) || (N != C && N != 4 * C) || rows <= 0 || rows > 0x7fffffffll) return SEGF_ERR_SHAPE;
+    if (!x || !gamma || !beta || !w || !bias || !out || !mean || !rstd) return SEGF_ERR_SHAPE;
+    if (y2 && !patch_geom_ok(rows, log2_w, log2_sr)) return SEGF_ERR_SHAPE;
+    if (((uintptr_t)x % 16) || ((uintptr_t)gamma % 16) || ((uintptr_t)beta % 16) || ((uintptr_t)w % 16) || ((uintptr_t)bias % 4) ||
+        ((uintptr_t)out % 16) || ((uintptr_t)y % 16) || ((uintptr_t)y2 % 16)) return SEGF_ERR_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = lnf_blocks(rows);
+#define LNF_GO(KS_, NT_, NCH_, Y_, Y2_) hipLaunchKernelGGL((ln_linear_fwd_kernel<KS_, NT_, NCH_, Y_, Y2_>), dim3(blocks), dim3(256), 0, st, (const bf16_t*)x, gamma, beta, \
+                           (const bf16_t*)w, bias, (bf16_t*)out, mean, rstd, (bf16_t*)y, (bf16_t*)y2, rows, eps, log2_w, log2_sr)
+#define LNF(KS_, NT_, NCH_) do { if (y) { if (y2) LNF_GO(KS_, NT_, NCH_, true, true); else LNF_GO(KS_, NT_, NCH_, true, false); } \
+                                 else { if (y2) LNF_GO(KS_, NT_, NCH_, false, true); else LNF_GO(KS_, NT_, NCH_, false, false); } } while (0)
+    // (K, N) -> the NT of the gemm_skinny_kernel<0, KS, NT> that segf_gemm takes for it (gemm.hip: gemm_skinny_nt)
+    if (C == 32 && N == 32) LNF(1, 2, 1);
+    else if (C == 32) LNF(1, 8, 1);
+    else if (N == 64) LNF(2, 4, 1);
+    else LNF(2, 8, 2);
+#undef LNF
+#undef LNF_GO
     SEGF_CHECK_LAUNCH();
     return 0;
 }

@@ -80,6 +80,7 @@
     X(loss_no_lse, "SEGFAC_LOSS_NO_LSE", 0, "the backward recomputes the softmax normalisation instead of taking the forward's per-pixel log-sum") \
     /* ---- LayerNorm (norm.hip) ---- */                                                                                                 \
     X(ln_linear_bwd_fused, "SEGFAC_LN_LINEAR_BWD_FUSED", 1, "Mix-FFN backward, fc1's data / weight / bias gradients formed inside the LayerNorm backward of norm2 (segf_layernorm_linear_bwd_supported): 0 = never, 1 = from 131072 token rows on, 2 = wherever the shape has the kernel") \
+    X(ln_linear_fwd_fused, "SEGFAC_LN_LINEAR_FWD_FUSED", 1, "MiT stages 1 / 2: LayerNorm as the operand prologue of its thin Linear (norm2 -> fc1, norm1 -> q; segf_layernorm_linear_fwd_supported), the LayerNorm output neither stored nor saved, and norm1 -> q's backward in one pass where SEGFAC_LN_LINEAR_BWD_FUSED allows it too: 0 = never, 1 = from 131072 token rows on, 2 = wherever the shape has the kernel") \
     /* ---- reductions (colreduce.h) ---- */                                                                                             \
     X(no_wide_finalize, "SEGFAC_NO_WIDE_FINALIZE", 0, "column-reduction finalize: one output per thread instead of four (bitwise the same sums)") \
     /* ---- [host] switches read by the Python layer ---- */                                                                             \

@@ -249,17 +249,17 @@ def defer_weight_grads():
         _SCALED_DY.clear()          # entries nobody collected must not outlive the backward they belong to (their addresses get reused)
 
 
-def _queue_dw(ctx, dy, x, n_out, n_in, tokens):
-    """Queue dW [n_out, n_in] = dy^T x and db = colsum(dy) of a Linear whose parameters both carry flat-gradient slots; False when the
-    product has to be issued by the caller (no scope, no slots)."""
+def _queue_dw(ctx, dy, x, n_out, n_in, tokens, iw=1, ib=2):
+    """Queue dW [n_out, n_in] = dy^T x and db = colsum(dy) of a Linear whose parameters (forward arguments iw, ib) both carry flat-gradient
+    slots; False when the product has to be issued by the caller (no scope, no slots)."""
     q = _DW_QUEUE
     slots = getattr(ctx, '_gslots', None)
-    if q is None or not slots or 1 not in slots or 2 not in slots:
+    if q is None or not slots or iw not in slots or ib not in slots:
         return False
-    gw, gb = slots[1][0].view(n_out, n_in), slots[2][0]
+    gw, gb = slots[iw][0].view(n_out, n_in), slots[ib][0]
     if gb.numel() != n_out or not gb.is_contiguous():
         return False
-    q.append(((dy, x, n_out, n_in, tokens, _splitk(n_out, n_in, tokens), gw, gb), (slots[1], slots[2]), None))
+    q.append(((dy, x, n_out, n_in, tokens, _splitk(n_out, n_in, tokens), gw, gb), (slots[iw], slots[ib]), None))
     if len(q) >= DW_QUEUE_MAX:
         flush_weight_grads()
     return True
@@ -591,63 +591,90 @@ def layer_norm_res(x, gamma, beta, eps):
     return LayerNormResFn.apply(x, gamma, beta, eps, *_dp_of(x))
 
 
+def _ln_linear_fwd_fused(x, g, b, w, bias):
+    """May the forward of Linear(LayerNorm(x)) run as hip.layernorm_linear_fwd?  The library's rule (SEGFAC_LN_LINEAR_FWD_FUSED) and the
+    16-byte alignment its vector loads of the parameters need."""
+    return (bias is not None and bias.dtype == torch.float32 and hip.layernorm_linear_fwd_supported(x.dtype, x.shape[0], x.shape[1], w.shape[0])
+            and all(t.data_ptr() % 16 == 0 for t in (x, g, b, w)) and bias.data_ptr() % 4 == 0)
+
+
+def _park_scaled(dx, rscale, rpg):
+    """dx.scaled (the DropPath-scaled copy a fused LayerNorm backward wrote) waits in _SCALED_DY for the backward of x's producer."""
+    if getattr(dx, 'scaled', None) is not None:
+        if len(_SCALED_DY) > 64:
+            _SCALED_DY.clear()
+        _SCALED_DY[dx.data_ptr()] = (dx.scaled, rscale.data_ptr(), rpg, dx._version)
+        dx.scaled = None
+
+
+def _ln_linear_bwd(ctx, dh, dres, x, g, b, mean, rstd, y, w, iw, ib, dy2=None, dy2_patch=None):
+    """hip.layernorm_linear_bwd for a formula whose forward arguments 1, 2 are the norm's parameters and iw, ib the Linear's: the four
+    parameter gradients written in place / deferred into the scope's grouped finalize where all four carry flat-gradient slots.
+    -> (dx, dgamma, dbeta, dw, dbias) with None for gradients that are delivered at the flush."""
+    N, K = w.shape
+    rscale, rpg = ctx.dp if ctx.dp is not None else (None, 1)
+    gg, gb, gw, gb1 = gslot(ctx, 1), gslot(ctx, 2), gslot(ctx, iw), gslot(ctx, ib)
+    outs = None
+    if (gg is not None and gb is not None and gw is not None and gb1 is not None and gb.data_ptr() == gg.data_ptr() + 4 * gg.numel()
+            and gw.is_contiguous() and gb1.is_contiguous()):
+        outs = (gw.view(N, K), gb1, gg, gb)
+    kw = dict(dres=dres, rscale=rscale, rows_per_group=rpg, outs=outs)
+    if y is None:
+        kw.update(beta=b, dy2=dy2, dy2_patch=dy2_patch)
+    q = _FIN_QUEUE
+    if q is not None and outs is not None:
+        slots = ctx._gslots
+        dx, items = hip.layernorm_linear_bwd(dh, w, x, y, g, mean, rstd, defer=True, **kw)
+        q.append((items[0], (slots[iw],)))
+        q.append((items[1], (slots[ib],)))
+        q.append((items[2], (slots[1], slots[2])))
+        if len(q) >= FIN_QUEUE_MAX:
+            _flush_finalizes()
+        res = (dx, None, None, None, None)
+    else:
+        dx, dw, db1, dg, db = hip.layernorm_linear_bwd(dh, w, x, y, g, mean, rstd, **kw)
+        res = (dx, dg, db, dw.view(ctx.wshape), db1)
+    _park_scaled(dx, rscale, rpg)                 # parked for the backward of x's producer, as _ln_bwd parks it
+    return res
+
+
 @direct_grads(1, 2, 4, 5)
 class LayerNormResLinearFn(Function):
     """(x, Linear(LayerNorm(x))): the pre-norm residual pattern of LayerNormResFn with the norm's only consumer, a C -> 4 C Linear (norm2 ->
     mlp.fc1 of a MiT block, mit.py:98,136-146), inside the same formula, so that the backward never writes the Linear's C-wide data gradient
     and reads the hidden-width gradient once: hip.layernorm_linear_bwd forms dy = dh W1, the LayerNorm backward of it and the four
-    parameter gradients in one pass.  The forward makes the two calls LayerNormResFn and LinearFn make; dx (and the DropPath-scaled copy
-    parked for the producer of x) carry the bits of that pair, the parameter gradients are the same sums in another order.  The choice of
-    this formula is made at forward time (layer_norm_res_linear_ok)."""
+    parameter gradients in one pass.  The forward is one pass too where the library has it for the size (hip.layernorm_linear_fwd: the
+    LayerNorm output is neither written nor saved, the backward rebuilds it from x), the two calls LayerNormResFn and LinearFn make
+    otherwise; either way h, dx (and the DropPath-scaled copy parked for the producer of x) carry the bits of that pair, the parameter
+    gradients are the same sums in another order.  The choice of this formula is made at forward time (layer_norm_res_linear_ok)."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, weight, bias, dp_scale=None, dp_rpg=1):
         ctx.dp = (dp_scale, int(dp_rpg)) if dp_scale is not None else None
         x = x if x.is_contiguous() else x.contiguous()
         g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        y, mean, rstd = hip.layernorm_fwd(x, g, b, eps)
         M, K = x.shape
         N = weight.shape[0]
         w = _w(weight.reshape(N, -1), x.dtype)
-        h = hip.gemm(0, y, w, M, N, K, bias=bias.detach())
-        ctx.save_for_backward(x, g, mean, rstd, y, w)
+        if _ln_linear_fwd_fused(x, g, b, w, bias.detach()):
+            h, mean, rstd, y, _ = hip.layernorm_linear_fwd(x, g, b, eps, w, bias.detach())
+        else:
+            y, mean, rstd = hip.layernorm_fwd(x, g, b, eps)
+            h = hip.gemm(0, y, w, M, N, K, bias=bias.detach())
+        ctx.save_for_backward(x, g, mean, rstd, y, w, b)
         ctx.wshape = weight.shape
         return x.view_as(x), h
 
     @staticmethod
     def backward(ctx, dres, dh):
-        x, g, mean, rstd, y, w = ctx.saved_tensors
+        x, g, mean, rstd, y, w, b = ctx.saved_tensors
         if dh is None:
             return dres, None, None, None, None, None, None, None
         dh = dh if dh.is_contiguous() else dh.contiguous()
         if dres is not None and not dres.is_contiguous():
             dres = dres.contiguous()
-        N, K = w.shape
-        rscale, rpg = ctx.dp if ctx.dp is not None else (None, 1)
-        gg, gb, gw, gb1 = gslot(ctx, 1), gslot(ctx, 2), gslot(ctx, 4), gslot(ctx, 5)
-        outs = None
-        if (gg is not None and gb is not None and gw is not None and gb1 is not None and gb.data_ptr() == gg.data_ptr() + 4 * gg.numel()
-                and gw.is_contiguous() and gb1.is_contiguous()):
-            outs = (gw.view(N, K), gb1, gg, gb)
-        q = _FIN_QUEUE
-        if q is not None and outs is not None:
-            slots = ctx._gslots
-            dx, items = hip.layernorm_linear_bwd(dh, w, x, y, g, mean, rstd, dres=dres, rscale=rscale, rows_per_group=rpg, outs=outs, defer=True)
-            q.append((items[0], (slots[4],)))
-            q.append((items[1], (slots[5],)))
-            q.append((items[2], (slots[1], slots[2])))
-            if len(q) >= FIN_QUEUE_MAX:
-                _flush_finalizes()
-            res = (dx, None, None, None, None, None, None, None)
-        else:
-            dx, dw, db1, dg, db = hip.layernorm_linear_bwd(dh, w, x, y, g, mean, rstd, dres=dres, rscale=rscale, rows_per_group=rpg, outs=outs)
-            res = (dx, dg, db, None, dw.view(ctx.wshape), db1, None, None)
-        if getattr(dx, 'scaled', None) is not None:          # parked for the backward of x's producer, as _ln_bwd parks it
-            if len(_SCALED_DY) > 64:
-                _SCALED_DY.clear()
-            _SCALED_DY[dx.data_ptr()] = (dx.scaled, rscale.data_ptr(), rpg, dx._version)
-            dx.scaled = None
-        return res
+        dx, dg, db, dw, db1 = _ln_linear_bwd(ctx, dh, dres, x, g, b, mean, rstd, y, w, 4, 5)
+        return dx, dg, db, None, dw, db1, None, None
 
 
 def layer_norm_res_linear_ok(x, gamma, beta, weight, bias):
@@ -700,6 +727,81 @@ class LayerNormResPatchFn(Function):
             dcol = dcol.contiguous()
         dx, dg, db = _ln_bwd(ctx, x, dy, g, mean, rstd, dy2=dcol, dres=dres, dy2_patch=ctx.patch if dcol is not None else None)
         return dx, dg, db, None, None, None, None, None
+
+
+@direct_grads(1, 2, 6, 7)
+class LayerNormResPatchLinearFn(Function):
+    """(x, Linear(LayerNorm(x)), im2col matrix of LayerNorm(x)): LayerNormResPatchFn with the norm's token-order consumer, the attention's
+    C -> C q Linear (mit.py:45,143), inside the same formula.  The forward is one pass (hip.layernorm_linear_fwd: the token-order LayerNorm
+    output is not written; only its patch-major copy is).  The backward is one pass as well where the library has it for the size
+    (hip.layernorm_linear_bwd with N = C: dy = dq Wq is never stored, the patch-major gradient joins it on load, y is rebuilt from x); else
+    the forward also keeps y and the backward makes the three launches LinearFn and LayerNormResPatchFn make.  q, col, dx and the
+    DropPath-scaled copy carry the bits of that pair of formulas; in the one-pass backward the four parameter gradients are the same sums in
+    another order."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, lw, ls, weight, bias, dp_scale=None, dp_rpg=1):
+        ctx.dp = (dp_scale, int(dp_rpg)) if dp_scale is not None else None
+        ctx.patch = (int(lw), int(ls))
+        x = x if x.is_contiguous() else x.contiguous()
+        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        M, K = x.shape
+        N = weight.shape[0]
+        w = _w(weight.reshape(N, -1), x.dtype)
+        if _ln_linear_fwd_fused(x, g, b, w, bias.detach()):
+            ctx.one_pass = bool(hip.layernorm_linear_bwd_ex_supported(x.dtype, M, K, N))
+            q, mean, rstd, y, col = hip.layernorm_linear_fwd(x, g, b, eps, w, bias.detach(), patch=ctx.patch, keep_y=not ctx.one_pass)
+        else:                                    # (a parameter view the vector loads cannot take: the two launches)
+            ctx.one_pass = False
+            y, mean, rstd, col = hip.layernorm_fwd(x, g, b, eps, patch=ctx.patch)
+            q = hip.gemm(0, y, w, M, N, K, bias=bias.detach())
+        ctx.save_for_backward(x, g, mean, rstd, y, w, b)
+        ctx.wshape = weight.shape
+        return x.view_as(x), q, col
+
+    @staticmethod
+    def backward(ctx, dres, dq, dcol):
+        x, g, mean, rstd, y, w, b = ctx.saved_tensors
+        none = (None,) * 10
+        if dq is None and dcol is None:
+            return (dres,) + none[1:]
+        if dq is None:
+            raise RuntimeError('layer_norm_res_patch_linear: the Linear output received no gradient')
+        dq = dq if dq.is_contiguous() else dq.contiguous()
+        if dres is not None and not dres.is_contiguous():
+            dres = dres.contiguous()
+        if dcol is not None and not dcol.is_contiguous():
+            dcol = dcol.contiguous()
+        patch = ctx.patch if dcol is not None else None
+        if ctx.one_pass:
+            dx, dg, db, dw, dbq = _ln_linear_bwd(ctx, dq, dres, x, g, b, mean, rstd, None, w, 6, 7, dy2=dcol, dy2_patch=patch)
+            return dx, dg, db, None, None, None, dw, dbq, None, None
+        # the three launches of LinearFn.backward + LayerNormResPatchFn.backward
+        M, K = x.shape
+        N = w.shape[0]
+        dy = hip.gemm(1, dq, w, M, K, N)
+        dw = dbq = None
+        if not _queue_dw(ctx, dq, y, N, K, M, 6, 7):
+            dw, dbq = hip.gemm_dw_db(dq, y, N, K, M, split_k=_splitk(N, K, M), out=gslot(ctx, 6, (N, K)), db_out=gslot(ctx, 7))
+            dw = dw.view(ctx.wshape)
+        dx, dg, db = _ln_bwd(ctx, x, dy, g, mean, rstd, dy2=dcol, dres=dres, dy2_patch=patch)
+        return dx, dg, db, None, None, None, dw, dbq, None, None
+
+
+def layer_norm_res_patch_linear_ok(x, gamma, beta, weight, bias):
+    """May (x, Linear(LayerNorm(x)), col) run as LayerNormResPatchLinearFn?  The library's rule for the one-pass forward
+    (segf_layernorm_linear_fwd_supported), a training pass, and all four parameters present and trained."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.ndim == 2 and torch.is_grad_enabled() and x.requires_grad):
+        return False
+    if bias is None or weight.ndim != 2 or not all(p.requires_grad for p in (gamma, beta, weight, bias)):
+        return False
+    return hip.layernorm_linear_fwd_supported(x.dtype, x.shape[0], x.shape[1], weight.shape[0])
+
+
+def layer_norm_res_patch_linear(x, gamma, beta, eps, W, sr, weight, bias):
+    """-> (x, Linear(LayerNorm(x)), im2col matrix of LayerNorm(x) for a k = s = sr convolution): use the returned x for the residual
+    connection.  Only where layer_norm_res_patch_linear_ok; layer_norm_res_patch + linear otherwise."""
+    return LayerNormResPatchLinearFn.apply(x, gamma, beta, eps, W.bit_length() - 1, sr.bit_length() - 1, weight, bias, *_dp_of(x))
 
 
 def patch_layout_ok(W, H, sr):

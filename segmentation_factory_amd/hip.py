@@ -681,6 +681,36 @@ def layernorm_fwd(x, gamma, beta, eps, patch=None):
     return y, mean, rstd
 
 
+def layernorm_linear_fwd_supported(dtype, rows, Cc, N):
+    """May Linear(LayerNorm(x)) with C -> N run as one forward pass (segf_layernorm_linear_fwd)?  Shape, size and policy rule of the library
+    (SEGFAC_LN_LINEAR_FWD_FUSED)."""
+    if dtype not in (torch.bfloat16, torch.float32):
+        return False
+    return bool(lib().segf_layernorm_linear_fwd_supported(BF16 if dtype == torch.bfloat16 else F32, int(rows), int(Cc), int(N)))
+
+
+def layernorm_linear_fwd(x, gamma, beta, eps, w, bias, patch=None, keep_y=False):
+    """out = Linear(LayerNorm(x)) in one pass, x [rows, C] bf16, w [N, C] bf16, bias fp32 [N] -> (out, mean, rstd, y, col): the LayerNorm output
+    is not stored unless asked for -- keep_y: y [rows, C] in token order; patch = (log2 W, log2 sr): col, the same rows in the patch-major order
+    of layernorm_fwd(..., patch=)."""
+    _need_cuda(x, gamma, beta, w, bias)
+    rows, Cc = x.shape
+    N = w.shape[0]
+    assert w.shape == (N, Cc) and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.is_contiguous() and w.is_contiguous()
+    assert bias.dtype == torch.float32 and bias.numel() == N and bias.is_contiguous()
+    out = torch.empty((rows, N), dtype=x.dtype, device=x.device)
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    y = torch.empty_like(x) if keep_y else None
+    col, lw, ls = None, 0, 0
+    if patch is not None:
+        lw, ls = patch
+        col = torch.empty((rows >> (2 * ls), Cc << (2 * ls)), dtype=x.dtype, device=x.device)
+    _chk(lib().segf_layernorm_linear_fwd(dt_of(x), rows, Cc, N, _ptr(x), _ptr(gamma), _ptr(beta), eps, _ptr(w), _ptr(bias), _ptr(out), _ptr(mean),
+                                         _ptr(rstd), _ptr(y), _ptr(col), lw, ls, _stream()), 'segf_layernorm_linear_fwd')
+    return out, mean, rstd, y, col
+
+
 def zeros(shape, dtype, device):
     """torch.zeros through the library's own fill kernel (keeps framework kernels out of the captured step)."""
     t = torch.empty(shape, dtype=dtype, device=device)
@@ -778,17 +808,35 @@ def layernorm_linear_bwd_supported(dtype, rows, Cc, N):
     return bool(lib().segf_layernorm_linear_bwd_supported(BF16 if dtype == torch.bfloat16 else F32, int(rows), int(Cc), int(N)))
 
 
-def layernorm_linear_bwd(dh, w1, x, y, gamma, mean, rstd, dres=None, rscale=None, rows_per_group=1, outs=None, defer=False, return_dy=False):
+def layernorm_linear_bwd_ex_supported(dtype, rows, Cc, N):
+    """layernorm_linear_bwd_supported for the general form (segf_layernorm_linear_bwd_ex): N = C as well as N = 4 C."""
+    if dtype not in (torch.bfloat16, torch.float32):
+        return False
+    return bool(lib().segf_layernorm_linear_bwd_ex_supported(BF16 if dtype == torch.bfloat16 else F32, int(rows), int(Cc), int(N)))
+
+
+def layernorm_linear_bwd(dh, w1, x, y, gamma, mean, rstd, dres=None, rscale=None, rows_per_group=1, outs=None, defer=False, return_dy=False,
+                         beta=None, dy2=None, dy2_patch=None):
     """dh [rows, N] bf16: gradient of Linear(LayerNorm(x)) with w1 [N, C] bf16, y = the saved LayerNorm output.
+    y = None (needs beta): the kernel rebuilds the LayerNorm output from x, mean, rstd, gamma, beta (segf_layernorm_linear_bwd_ex); then N = C
+    is served too, with dy2 = a second consumer's gradient of the LayerNorm output added to dh w1 (dy2_patch = (log2 W, log2 sr): dy2 in
+    patch-major row order, as layernorm_bwd takes it).
     -> (dx, dw1, db1, dgamma, dbeta) with the parameter gradients fp32; `dx.scaled` = dx * rscale[row / rows_per_group] when rscale is given.
     outs = (dw1 [N, C], db1 [N], dgamma [C], dbeta [C]) fp32 targets written in place (dbeta adjacent to dgamma: dbeta == dgamma + C).
     defer=True (needs outs): the kernel leaves its per-workgroup partial sums and (dx, [three finalize items]) is returned; the caller
     passes the items to colreduce_finalize_grouped later.  return_dy: the Linear's data gradient [rows, C] is appended to the result."""
     rows, Cc = x.shape
     N = w1.shape[0]
-    _need_cuda(dh, w1, x, y, gamma, mean, rstd)
-    assert dh.shape == (rows, N) and w1.shape == (N, Cc) and y.shape == x.shape
-    assert all(t.dtype == torch.bfloat16 and t.is_contiguous() for t in (dh, w1, x, y))
+    _need_cuda(dh, w1, x, gamma, mean, rstd)
+    assert dh.shape == (rows, N) and w1.shape == (N, Cc)
+    assert all(t.dtype == torch.bfloat16 and t.is_contiguous() for t in (dh, w1, x))
+    if y is not None:
+        _need_cuda(y)
+        assert y.shape == x.shape and y.dtype == torch.bfloat16 and y.is_contiguous() and dy2 is None
+    else:
+        _need_cuda(beta)
+        assert beta is not None and beta.dtype == torch.float32 and beta.numel() == Cc and beta.is_contiguous()
+        assert dy2 is None or (dy2.numel() == x.numel() and dy2.dtype == x.dtype and dy2.is_contiguous() and (dy2_patch is not None or dy2.shape == x.shape))
     assert dres is None or (dres.shape == x.shape and dres.dtype == x.dtype and dres.is_contiguous())
     dx = torch.empty_like(x)
     dxs = None
@@ -809,9 +857,15 @@ def layernorm_linear_bwd(dh, w1, x, y, gamma, mean, rstd, dres=None, rscale=None
         dg, db = dgb[0], dgb[1]
     ws = _f32(lib().segf_layernorm_linear_bwd_ws(rows, Cc, N), x.device)
     now = [None] * 4 if defer else [dw.data_ptr(), db1.data_ptr(), dg.data_ptr(), db.data_ptr()]
-    _chk(lib().segf_layernorm_linear_bwd(dt_of(x), rows, Cc, N, _ptr(dh), _ptr(w1), _ptr(x), _ptr(y), _ptr(dres), _ptr(gamma), _ptr(mean),
-                                         _ptr(rstd), _ptr(dx), _ptr(rscale), int(rows_per_group), _ptr(dxs), _ptr(dyo), *now, _ptr(ws),
-                                         _stream()), 'segf_layernorm_linear_bwd')
+    if y is not None:
+        _chk(lib().segf_layernorm_linear_bwd(dt_of(x), rows, Cc, N, _ptr(dh), _ptr(w1), _ptr(x), _ptr(y), _ptr(dres), _ptr(gamma), _ptr(mean),
+                                             _ptr(rstd), _ptr(dx), _ptr(rscale), int(rows_per_group), _ptr(dxs), _ptr(dyo), *now, _ptr(ws),
+                                             _stream()), 'segf_layernorm_linear_bwd')
+    else:
+        lw, ls = dy2_patch if (dy2_patch is not None and dy2 is not None) else (-1, 0)
+        _chk(lib().segf_layernorm_linear_bwd_ex(dt_of(x), rows, Cc, N, _ptr(dh), _ptr(w1), _ptr(x), None, _ptr(beta), _ptr(dy2), lw, ls, _ptr(dres),
+                                                _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(rscale), int(rows_per_group), _ptr(dxs),
+                                                _ptr(dyo), *now, _ptr(ws), _stream()), 'segf_layernorm_linear_bwd_ex')
     dx.scaled = dxs
     if defer:
         nblk = int(lib().segf_layernorm_linear_bwd_blocks(rows))
