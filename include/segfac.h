@@ -385,6 +385,44 @@ int segf_group_attention_bwd(int dt, int B, int H, int W, int heads, int hd, int
                              int64_t ldqkv, const float* bias, float scale, const void* d_o, int64_t lddo, const float* lse,
                              void* dqkv, int64_t lddqkv, float* dbias, float* ws, void* stream);
 
+/* ---- CAS-ViT additive token mixer (casvit.py:68-92, 112-138; csrc/token_mixer.hip): three streaming kernel pairs on token tensors
+ * [M = B HW][C] of B samples with HW pixels each, in the storage dtype; gates, reductions and their results are fp32.
+ * Rules common to all of them (anything else returns SEGF_ERR_SHAPE before any launch, and the *_supported queries answer 0):
+ * 0 < B <= 65535, HW > 0; C % 8 == 0 and 8 <= C <= 1024; B HW < 2^31 / 4; every leading dimension (elements between rows) >= C with 16-byte aligned
+ * rows (ld % 8 == 0 for bf16, ld % 4 == 0 for fp32, base pointers 16-byte aligned), so an operand may be a column slice of a wider
+ * buffer such as the [M][3 C] qkv product; columns outside the slice are neither read nor written.  The *_supported queries take the
+ * SMALLEST alignment-relevant leading dimension the caller will pass.  Sums over pixels / rows are per-workgroup partial sums in the
+ * caller's workspace (the *_ws queries give its size in floats) added in a fixed order: no floating-point atomics, two runs give the
+ * same bits.  Nothing is allocated.
+ *
+ * spatial gate (SpatialOperation's tail + the pooled sum of ChannelOperation): r [M][C] (contiguous) is the BatchNorm + ReLU output,
+ * w [C] fp32 the 1 x 1 convolution to one channel:  s[m] = sigmoid(sum_c r[m][c] w[c]) (fp32 [M]),  y = x * s (ldy),
+ * pool[b][c] = sum over the pixels of sample b of the UNROUNDED fp32 product x * s (fp32 [B][C]; the caller divides by HW).
+ * Backward: g = dy + dpool[b] (dpool fp32 [B][C], may be null);  dx = g * s (lddx);  ds = sum_c g * x;  dl = ds s (1 - s);
+ * dr = dl * w ([M][C] contiguous);  dw[c] = sum_m dl[m] r[m][c] (fp32). */
+int segf_spatial_gate_supported(int dt, int B, int HW, int C, int64_t ld);
+int64_t segf_spatial_gate_fwd_ws(int B, int HW, int C);
+int segf_spatial_gate_fwd(int dt, int B, int HW, int C, const void* x, int64_t ldx, const void* r, const float* w, float* s, void* y,
+                          int64_t ldy, float* pool, float* ws, void* stream);
+int64_t segf_spatial_gate_bwd_ws(int B, int HW, int C);
+int segf_spatial_gate_bwd(int dt, int B, int HW, int C, const void* dy, int64_t lddy, const float* dpool, const void* x, int64_t ldx,
+                          const void* r, const float* s, const float* w, void* dx, int64_t lddx, void* dr, float* dw, float* ws,
+                          void* stream);
+/* channel gate mix (ChannelOperation of q and of k, and their sum):  u = q1 * gq[b] + k1 * gk[b], gq / gk fp32 [B][C].
+ * Backward: dq1 = du * gq[b], dk1 = du * gk[b], dgq[b][c] = sum over the pixels of sample b of du * q1, dgk likewise with k1 (fp32 [B][C]). */
+int segf_channel_gate_mix_supported(int dt, int B, int HW, int C, int64_t ld);
+int segf_channel_gate_mix_fwd(int dt, int B, int HW, int C, const void* q1, int64_t ldq, const void* k1, int64_t ldk, const float* gq,
+                              const float* gk, void* u, int64_t ldu, void* stream);
+int64_t segf_channel_gate_mix_bwd_ws(int B, int HW, int C);
+int segf_channel_gate_mix_bwd(int dt, int B, int HW, int C, const void* du, int64_t lddu, const void* q1, int64_t ldq, const void* k1,
+                              int64_t ldk, const float* gq, const float* gk, void* dq1, int64_t lddq, void* dk1, int64_t lddk, float* dgq,
+                              float* dgk, float* ws, void* stream);
+/* gated product:  z = a * v;  backward da = dz * v, dv = dz * a.  M rows (M < 2^31 / 4). */
+int segf_gated_mul_supported(int dt, int M, int C, int64_t ld);
+int segf_gated_mul_fwd(int dt, int M, int C, const void* a, int64_t lda, const void* v, int64_t ldv, void* z, int64_t ldz, void* stream);
+int segf_gated_mul_bwd(int dt, int M, int C, const void* dz, int64_t lddz, const void* a, int64_t lda, const void* v, int64_t ldv,
+                       void* da, int64_t ldda, void* dv, int64_t lddv, void* stream);
+
 /* ---- depthwise 3x3 conv + bias + GELU(erf) on NHWC (mit.py:62-71,98-99 DWConv -> F.gelu) ----------- */
 int segf_dwconv3x3_gelu_fwd(int dt, int B, int H, int W, int C, const void* x, const float* w /*[C][9]*/,
                             const float* bias, int apply_gelu, void* y, void* stream);

@@ -791,3 +791,174 @@ def crossformer_base(**kw):
 
 def crossformer_large(**kw):
     return CrossFormer(embed_dim=128, depths=[2, 2, 18, 2], num_heads=[4, 8, 16, 32], **kw)
+
+
+# ---- CAS-ViT / RCViT (models/backbones/casvit.py) -------------------------------------------------------------------------------
+class _SpatialOperation(nn.Module):
+    """casvit.py:68-80: x * sigmoid(conv1x1_to_1(ReLU(BN(dw3x3(x))))); keys block.{0,1,3}.* (ReLU at 2, Sigmoid at 4)."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.block = nn.Sequential(ConvWeights(dim, dim, 3, 1, 1, groups=dim), BatchNormWeights(dim), nn.Identity(),
+                                   ConvWeights(dim, 1, 1, 1, 0, bias=False), nn.Identity())
+
+
+class _ChannelOperation(nn.Module):
+    """casvit.py:82-92: x * sigmoid(Wc mean_pixels(x)); key block.1.weight (the pool at 0, Sigmoid at 2)."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.block = nn.Sequential(nn.Identity(), ConvWeights(dim, dim, 1, 1, 0, bias=False), nn.Identity())
+
+
+class _LocalIntegration(nn.Module):
+    """casvit.py:94-109 as Stage builds it: conv1x1 -> BatchNorm -> depthwise 3x3 -> GELU -> conv1x1; keys network.{0,1,2,4}.*."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.network = nn.Sequential(ConvWeights(dim, dim, 1, 1, 0), BatchNormWeights(dim), ConvWeights(dim, dim, 3, 1, 1, groups=dim),
+                                     nn.Identity(), ConvWeights(dim, dim, 1, 1, 0))
+
+
+class AdditiveTokenMixer(nn.Module):
+    """casvit.py:112-138: proj(dwc(ChannelOp(SpatialOp(q)) + ChannelOp(SpatialOp(k))) * v), q, k, v = chunk3(conv1x1(x))."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.dim = dim
+        self.qkv = ConvWeights(dim, 3 * dim, 1, 1, 0, bias=False)
+        self.oper_q = nn.Sequential(_SpatialOperation(dim), _ChannelOperation(dim))
+        self.oper_k = nn.Sequential(_SpatialOperation(dim), _ChannelOperation(dim))
+        self.dwc = ConvWeights(dim, dim, 3, 1, 1, groups=dim)
+        self.proj = ConvWeights(dim, dim, 3, 1, 1, groups=dim)
+
+    @staticmethod
+    def _gated(oper, t, B, H, W, training):
+        """(SpatialOp(t), ChannelOp's gate [B, C] fp32).  t feeds the gate's depthwise conv and the gated product: a fork."""
+        sp, ch = oper[0].block, oper[1].block
+        ta, tb = Fh.fork(t, 2)
+        r = Fh.dwconv3x3_gelu(ta, sp[0].weight, sp[0].bias, B, H, W, False)
+        r = _bn_act(r, sp[1], training, 1)
+        y, pool = Fh.spatial_gate(tb, r, sp[3].weight, B, H * W)
+        # the channel gate: a [B, C] x [C, C] product per operator, fp32 torch ops on the current stream (off the hot path, captured into
+        # the step's graph like DynamicPosBias.bias); autograd carries the kernels' gate gradients back to the weight and to `pool`
+        C = pool.shape[1]
+        gate = torch.sigmoid(((pool * (1.0 / (H * W))).unsqueeze(1) * ch[1].weight.view(C, C).unsqueeze(0)).sum(-1))
+        return y, gate
+
+    def tokens(self, x, B, H, W, training):
+        q, k, v = Fh.qkv_split3(x, self.qkv.weight)
+        q1, gq = self._gated(self.oper_q, q, B, H, W, training)
+        k1, gk = self._gated(self.oper_k, k, B, H, W, training)
+        u = Fh.channel_gate_mix(q1, k1, gq, gk, B, H * W)
+        a = Fh.dwconv3x3_gelu(u, self.dwc.weight, self.dwc.bias, B, H, W, False)
+        z = Fh.gated_mul(a, v)
+        return Fh.dwconv3x3_gelu(z, self.proj.weight, self.proj.bias, B, H, W, False)
+
+
+class _RCViTMlp(nn.Module):
+    def __init__(self, dim, hidden):
+        super().__init__()
+        self.fc1 = ConvWeights(dim, hidden, 1)
+        self.fc2 = ConvWeights(hidden, dim, 1)
+
+
+class AdditiveBlock(nn.Module):
+    """casvit.py:142-162 as Stage builds it (norm_layer = BatchNorm2d, act_layer = GELU, drop = drop_path = 0: no stochastic module):
+    x + LocalIntegration(x);  x + mixer(BN(x));  x + fc2(GELU(fc1(BN(x))))."""
+
+    def __init__(self, dim, mlp_ratio=4.):
+        super().__init__()
+        self.local_perception = _LocalIntegration(dim)
+        self.norm1 = BatchNormWeights(dim)
+        self.attn = AdditiveTokenMixer(dim)
+        self.norm2 = BatchNormWeights(dim)
+        self.mlp = _RCViTMlp(dim, int(dim * mlp_ratio))
+
+    def tokens(self, x, B, H, W, training):
+        li = self.local_perception.network
+        x, h = Fh.fork(x, 2)
+        h = _bn_act(Fh.linear(h, li[0].weight, li[0].bias), li[1], training, 0)
+        h = Fh.dwconv3x3_gelu(h, li[2].weight, li[2].bias, B, H, W, True)
+        x = Fh.linear(h, li[4].weight, li[4].bias, residual=x)
+        x, h = Fh.fork(x, 2)
+        x = Fh.add(x, self.attn.tokens(_bn_act(h, self.norm1, training, 0), B, H, W, training))
+        x, h = Fh.fork(x, 2)
+        f = Fh.gelu(Fh.linear(_bn_act(h, self.norm2, training, 0), self.mlp.fc1.weight, self.mlp.fc1.bias))
+        return Fh.linear(f, self.mlp.fc2.weight, self.mlp.fc2.bias, residual=x)
+
+
+class _RCViTEmbedding(nn.Module):
+    """casvit.py:28-48 between stages: conv k3 s2 p1 (bias) + BatchNorm."""
+
+    def __init__(self, c1, c2):
+        super().__init__()
+        self.proj = ConvWeights(c1, c2, 3, 2, 1)
+        self.norm = BatchNormWeights(c2)
+
+
+class RCViT(nn.Module):
+    """models/backbones/casvit.py:181-278 with fork_feat=True as its factories build it: a two-convolution stem (k3 s2 p1 + BN + ReLU,
+    twice), four stages of AdditiveBlocks with a k3 s2 p1 Embedding between them, and a BatchNorm norm{0,2,4,6} on the copy of each stage
+    output that goes to the decode head (the un-normed tensor continues).  No drop path (the factories pass no rate), no dropout.
+    Every conv and BatchNorm keeps torch's default initialisation (cls_init_weights touches nn.Linear only, :242-246)."""
+
+    def __init__(self, layers, embed_dims, mlp_ratios=4):
+        super().__init__()
+        self.channels = list(embed_dims)
+        self.compute_dtype = torch.bfloat16
+        c0 = embed_dims[0]
+        self.patch_embed = nn.Sequential(ConvWeights(3, c0 // 2, 3, 2, 1), BatchNormWeights(c0 // 2), nn.Identity(),
+                                         ConvWeights(c0 // 2, c0, 3, 2, 1), BatchNormWeights(c0), nn.Identity())
+        network = []
+        for i in range(len(layers)):
+            network.append(nn.Sequential(*[AdditiveBlock(embed_dims[i], mlp_ratios) for _ in range(layers[i])]))
+            if i < len(layers) - 1:
+                network.append(_RCViTEmbedding(embed_dims[i], embed_dims[i + 1]))
+        self.network = nn.ModuleList(network)
+        self.out_indices = [0, 2, 4, 6]
+        for i_emb, i_layer in enumerate(self.out_indices):
+            self.add_module(f'norm{i_layer}', BatchNormWeights(embed_dims[i_emb]))
+
+    def forward_tokens(self, x):
+        """x: fp32 NCHW image.  Returns 4 TokenMaps (strides 4/8/16/32)."""
+        B, _, H, W = x.shape
+        tr = self.training
+        pe = self.patch_embed
+        t = Fh.conv_patch(x, pe[0].weight, pe[0].bias, (B, H, W, 3, 3, 2, 1), image=True, dtype=self.compute_dtype)
+        H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        t = _bn_act(t, pe[1], tr, 1)
+        t = Fh.conv_patch(t, pe[3].weight, pe[3].bias, (B, H, W, pe[3].in_channels, 3, 2, 1))
+        H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        t = _bn_act(t, pe[4], tr, 1)
+        outs = []
+        for idx, m in enumerate(self.network):
+            if isinstance(m, _RCViTEmbedding):
+                t = Fh.conv_patch(t, m.proj.weight, m.proj.bias, (B, H, W, m.proj.in_channels, 3, 2, 1))
+                H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+                t = _bn_act(t, m.norm, tr, 0)
+                continue
+            for blk in m:
+                t = blk.tokens(t, B, H, W, tr)
+            if idx != len(self.network) - 1:
+                t, th = Fh.fork(t, 2)                # the stage output feeds its output norm and the next Embedding
+            else:
+                th = t
+            outs.append(TokenMap(_bn_act(th, getattr(self, f'norm{idx}'), tr, 0), B, H, W))
+        return outs
+
+    def forward(self, x):
+        return [tm.nchw() for tm in self.forward_tokens(x)]
+
+
+# the reference's factories (casvit.py:283-313)
+def rcvit_s(**kw):
+    return RCViT(layers=[3, 3, 6, 3], embed_dims=[48, 64, 128, 256], **kw)
+
+
+def rcvit_m(**kw):
+    return RCViT(layers=[3, 3, 6, 3], embed_dims=[64, 96, 192, 384], **kw)
+
+
+def rcvit_t(**kw):
+    return RCViT(layers=[3, 3, 6, 3], embed_dims=[96, 128, 256, 512], **kw)

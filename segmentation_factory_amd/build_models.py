@@ -20,7 +20,14 @@ backbone_registry = {'MiT': _backbones.MiT, 'ConvNeXt': _backbones.ConvNeXt, 'Co
                      'MobileNetV2': _backbones.MobileNetV2}
 backbone_registry.update({n: getattr(_backbones, n) for n in (
     'convnextv2_atto', 'convnextv2_femto', 'convnext_pico', 'convnextv2_nano', 'convnextv2_tiny', 'convnextv2_base',
-    'convnextv2_large', 'convnextv2_huge', 'crossformer_tiny', 'crossformer_small', 'crossformer_base', 'crossformer_large')})
+    'convnextv2_large', 'convnextv2_huge', 'crossformer_tiny', 'crossformer_small', 'crossformer_base', 'crossformer_large',
+    'rcvit_s', 'rcvit_m', 'rcvit_t')})
+# names of the reference that are deliberately absent, and why (the KeyError says it)
+unavailable_backbones = {
+    'rcvit_xs': 'its stage widths 56, 112 and 220 are outside the kernels\' channel rule (rows of 16-byte chunks: 220 is not a multiple '
+                'of 8, and the token-mixer kernels refuse it on the host; 56 and 112 are widths no GEMM or depthwise kernel of this '
+                'library is verified at); rcvit_s, rcvit_m and rcvit_t are available',
+}
 head_dict = {'SegFormerHead': _heads.SegFormerHead, 'UPerHead': _heads.UPerHead, 'FPNHead': _heads.FPNHead}
 
 
@@ -55,6 +62,8 @@ class SegmentationModel(BaseSegModel):
             self.backbone = backbone_registry[family](variant)
             name_for_width = family          # quirk Q1: the name has been rebound to 'MiT' before the width test
         else:
+            if backbone in unavailable_backbones and backbone not in backbone_registry:
+                raise KeyError(f'backbone {backbone!r} is not available in the MI355X path: {unavailable_backbones[backbone]}')
             if backbone not in backbone_registry:
                 raise KeyError(f'backbone {backbone!r} is not available in the MI355X path; have {sorted(backbone_registry)}')
             self.backbone = backbone_registry[backbone]()

@@ -1091,6 +1091,124 @@ def group_attention(qkv, bias, B, H, W, heads, G, interval, lda):
     return GroupAttentionFn.apply(qkv, bias, B, H, W, heads, G, interval, bool(lda))
 
 
+# ---- CAS-ViT additive token mixer (casvit.py:68-92, 112-138; csrc/token_mixer.hip) ------------------------------------------------
+@direct_grads(1)
+class QkvSplit3Fn(Function):
+    """q, k, v = chunk3(x W^T) (casvit.py:118,133; no bias) as three CONTIGUOUS [M, C] tensors: the three row blocks of the [3C, C] weight
+    are multiplied one by one, because q and k go on into the depthwise 3x3 kernels, which take contiguous rows.  The backward
+    gathers the three gradients into the columns of one [M, 3C] buffer with the library's copy kernel (one grouped launch) and runs the two
+    products of a 3C-wide Linear on it."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        x = _rowmajor(x)
+        M, K = x.shape
+        N = weight.shape[0]
+        assert N % 3 == 0
+        Cq = N // 3
+        w = _w(weight.reshape(N, -1), x.dtype)
+        outs = tuple(hip.gemm(0, x, w[i * Cq:(i + 1) * Cq], M, Cq, K) for i in range(3))
+        ctx.save_for_backward(x, w)
+        ctx.meta = (M, N, K, weight.shape)
+        return outs
+
+    @staticmethod
+    def backward(ctx, dq, dk, dv):
+        x, w = ctx.saved_tensors
+        M, N, K, wshape = ctx.meta
+        Cq = N // 3
+        dqkv = torch.empty((M, N), dtype=x.dtype, device=x.device)
+        jobs = []
+        for i, d in enumerate((dq, dk, dv)):
+            sl = dqkv[:, i * Cq:(i + 1) * Cq]
+            jobs.append(('cast', _rowmajor(d), sl) if d is not None else ('zero', sl))
+        hip.prep_grouped(jobs)
+        dx = hip.gemm(1, dqkv, w, M, K, N) if ctx.needs_input_grad[0] else None
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dw = hip.gemm(2, dqkv, x, N, K, M, out=gslot(ctx, 1, (N, K)), out_dtype=torch.float32, split_k=_splitk(N, K, M)).view(wshape)
+        return dx, dw
+
+
+def qkv_split3(x, weight):
+    return QkvSplit3Fn.apply(x, weight)
+
+
+@direct_grads(2)
+class SpatialGateFn(Function):
+    """(x * s, sum over each sample's pixels of x * s) with s = sigmoid(conv1x1_to_one_channel(r)), r = ReLU(BN(dw3x3(x) + b)):
+    SpatialOperation's tail and ChannelOperation's pooled sum (casvit.py:75-80, 86).  Kernel: spatial_gate_fwd_kernel / _bwd_kernel."""
+
+    @staticmethod
+    def forward(ctx, x, r, weight, B, HW):
+        r = r if r.is_contiguous() else r.contiguous()
+        x = _rowmajor(x)
+        w = weight.detach().reshape(-1).contiguous()
+        y, s, pool = hip.spatial_gate_fwd(x, r, w, B, HW)
+        ctx.save_for_backward(x, r, s, w)
+        ctx.meta = (B, HW, weight.shape)
+        return y, pool
+
+    @staticmethod
+    def backward(ctx, dy, dpool):
+        x, r, s, w = ctx.saved_tensors
+        B, HW, wshape = ctx.meta
+        if dy is None:
+            dy = hip.zeros((B * HW, w.numel()), x.dtype, x.device)
+        if dpool is not None:
+            dpool = dpool.detach().float().contiguous()
+        dx, dr, dw = hip.spatial_gate_bwd(_rowmajor(dy), dpool, x, r, s, w, B, HW)
+        return dx, dr, dw.view(wshape), None, None
+
+
+def spatial_gate(x, r, weight, B, HW):
+    return SpatialGateFn.apply(x, r, weight, B, HW)
+
+
+class ChannelGateMixFn(Function):
+    """u = q1 * gq[b] + k1 * gk[b]: the two ChannelOperation products and the q + k of casvit.py:92,136 in one pass; gq, gk fp32 [B, C].
+    Kernel: channel_gate_mix_fwd_kernel / _bwd_kernel."""
+
+    @staticmethod
+    def forward(ctx, q1, k1, gq, gk, B, HW):
+        q1, k1 = _rowmajor(q1), _rowmajor(k1)
+        gq, gk = gq.detach().float().contiguous(), gk.detach().float().contiguous()
+        u = hip.channel_gate_mix_fwd(q1, k1, gq, gk, B, HW)
+        ctx.save_for_backward(q1, k1, gq, gk)
+        ctx.meta = (B, HW)
+        return u
+
+    @staticmethod
+    def backward(ctx, du):
+        q1, k1, gq, gk = ctx.saved_tensors
+        B, HW = ctx.meta
+        dq1, dk1, dgq, dgk = hip.channel_gate_mix_bwd(_rowmajor(du), q1, k1, gq, gk, B, HW)
+        return dq1, dk1, dgq, dgk, None, None
+
+
+def channel_gate_mix(q1, k1, gq, gk, B, HW):
+    return ChannelGateMixFn.apply(q1, k1, gq, gk, B, HW)
+
+
+class GatedMulFn(Function):
+    """z = a * v (casvit.py:136: dwc(q + k) * v).  Kernel: gated_mul_fwd_kernel / _bwd_kernel."""
+
+    @staticmethod
+    def forward(ctx, a, v):
+        a, v = _rowmajor(a), _rowmajor(v)
+        ctx.save_for_backward(a, v)
+        return hip.gated_mul_fwd(a, v)
+
+    @staticmethod
+    def backward(ctx, dz):
+        a, v = ctx.saved_tensors
+        return hip.gated_mul_bwd(_rowmajor(dz), a, v)
+
+
+def gated_mul(a, v):
+    return GatedMulFn.apply(a, v)
+
+
 @direct_grads(1, 2)
 class DWConvGeluFn(Function):
     """gelu(depthwise3x3(x) + b) on NHWC tokens (mit.py:62-71 + F.gelu at :99)."""

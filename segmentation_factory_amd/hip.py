@@ -1057,6 +1057,114 @@ def group_attention_bwd(qkv, bias, d_o, lse, B, H, W, heads, G, interval, lda, s
     return dqkv, dbias
 
 
+# ---- CAS-ViT additive token mixer (csrc/token_mixer.hip) ---------------------------------------------------------------------
+def _token_mixer_check(what, supported, B, HW, Cc, *ops):
+    """The refusal happens here, on the host, before any launch.  ops: the [rows, >= Cc] operands that may be column slices."""
+    for t in ops:
+        assert t.ndim == 2 and t.shape[0] == B * HW and t.shape[1] >= Cc and (t.stride(1) == 1 or t.shape[1] == 1), (what, tuple(t.shape))
+    if not all(supported(dt_of(ops[0]), B, HW, Cc, ld) for ld in sorted({max(t.stride(0), Cc) if t.shape[0] == 1 else t.stride(0) for t in ops})):
+        raise RuntimeError(f'{what}: no kernel for {B} x {HW} rows of {Cc} channels (leading dimensions {[t.stride(0) for t in ops]}): the '
+                           f'channel count must be a multiple of 8 and at most 1024, B * HW below 2^29, rows 16-byte aligned '
+                           f'(there is no fallback path)')
+    for t in ops:
+        assert t.data_ptr() % 16 == 0, f'{what}: operand not 16-byte aligned'
+
+
+def spatial_gate_fwd(x, r, w, B, HW):
+    """x: [B*HW, C] (any aligned row stride), r: [B*HW, C] contiguous, w: [C] fp32 -> (y [B*HW, C], s [B*HW] fp32, pool [B, C] fp32)."""
+    _need_cuda(x, r, w)
+    Cc = w.numel()
+    _token_mixer_check('spatial gate', lib().segf_spatial_gate_supported, B, HW, Cc, x, r)
+    assert r.is_contiguous() and r.shape[1] == Cc and r.dtype == x.dtype and w.dtype == torch.float32 and w.is_contiguous()
+    y = torch.empty((B * HW, Cc), dtype=x.dtype, device=x.device)
+    s = torch.empty(B * HW, dtype=torch.float32, device=x.device)
+    pool = torch.empty((B, Cc), dtype=torch.float32, device=x.device)
+    ws = _f32(lib().segf_spatial_gate_fwd_ws(B, HW, Cc), x.device)
+    _chk(lib().segf_spatial_gate_fwd(dt_of(x), B, HW, Cc, _ptr(x), x.stride(0), _ptr(r), _ptr(w), _ptr(s), _ptr(y), y.stride(0), _ptr(pool),
+                                     _ptr(ws), _stream()), 'segf_spatial_gate_fwd')
+    return y, s, pool
+
+
+def spatial_gate_bwd(dy, dpool, x, r, s, w, B, HW, dx=None):
+    """-> (dx [B*HW, C] (or written into the given view), dr [B*HW, C], dw [C] fp32); dpool: [B, C] fp32 or None."""
+    _need_cuda(dy, x, r, s, w)
+    Cc = w.numel()
+    if dx is None:
+        dx = torch.empty((B * HW, Cc), dtype=x.dtype, device=x.device)
+    _token_mixer_check('spatial gate backward', lib().segf_spatial_gate_supported, B, HW, Cc, dy, x, r, dx)
+    assert dpool is None or (dpool.is_contiguous() and dpool.dtype == torch.float32 and tuple(dpool.shape) == (B, Cc))
+    assert r.is_contiguous() and s.is_contiguous() and s.numel() == B * HW and dy.dtype == x.dtype == r.dtype == dx.dtype
+    dr = torch.empty((B * HW, Cc), dtype=x.dtype, device=x.device)
+    dw = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    ws = _f32(lib().segf_spatial_gate_bwd_ws(B, HW, Cc), x.device)
+    _chk(lib().segf_spatial_gate_bwd(dt_of(x), B, HW, Cc, _ptr(dy), dy.stride(0), _ptr(dpool), _ptr(x), x.stride(0), _ptr(r), _ptr(s),
+                                     _ptr(w), _ptr(dx), dx.stride(0), _ptr(dr), _ptr(dw), _ptr(ws), _stream()), 'segf_spatial_gate_bwd')
+    return dx, dr, dw
+
+
+def channel_gate_mix_fwd(q1, k1, gq, gk, B, HW):
+    """u = q1 * gq[b] + k1 * gk[b];  gq, gk: [B, C] fp32."""
+    _need_cuda(q1, k1, gq, gk)
+    Cc = gq.shape[1]
+    _token_mixer_check('channel gate mix', lib().segf_channel_gate_mix_supported, B, HW, Cc, q1, k1)
+    assert gq.is_contiguous() and gk.is_contiguous() and gq.dtype == gk.dtype == torch.float32 and tuple(gq.shape) == tuple(gk.shape) == (B, Cc)
+    assert q1.dtype == k1.dtype
+    u = torch.empty((B * HW, Cc), dtype=q1.dtype, device=q1.device)
+    _chk(lib().segf_channel_gate_mix_fwd(dt_of(q1), B, HW, Cc, _ptr(q1), q1.stride(0), _ptr(k1), k1.stride(0), _ptr(gq), _ptr(gk), _ptr(u),
+                                         u.stride(0), _stream()), 'segf_channel_gate_mix_fwd')
+    return u
+
+
+def channel_gate_mix_bwd(du, q1, k1, gq, gk, B, HW, dq1=None, dk1=None):
+    """-> (dq1, dk1 [B*HW, C] (or written into the given views), dgq, dgk [B, C] fp32)."""
+    _need_cuda(du, q1, k1, gq, gk)
+    Cc = gq.shape[1]
+    if dq1 is None:
+        dq1 = torch.empty((B * HW, Cc), dtype=q1.dtype, device=q1.device)
+    if dk1 is None:
+        dk1 = torch.empty((B * HW, Cc), dtype=q1.dtype, device=q1.device)
+    _token_mixer_check('channel gate mix backward', lib().segf_channel_gate_mix_supported, B, HW, Cc, du, q1, k1, dq1, dk1)
+    assert gq.is_contiguous() and gk.is_contiguous() and du.dtype == q1.dtype == k1.dtype == dq1.dtype == dk1.dtype
+    dgq = torch.empty((B, Cc), dtype=torch.float32, device=q1.device)
+    dgk = torch.empty((B, Cc), dtype=torch.float32, device=q1.device)
+    ws = _f32(lib().segf_channel_gate_mix_bwd_ws(B, HW, Cc), q1.device)
+    _chk(lib().segf_channel_gate_mix_bwd(dt_of(q1), B, HW, Cc, _ptr(du), du.stride(0), _ptr(q1), q1.stride(0), _ptr(k1), k1.stride(0),
+                                         _ptr(gq), _ptr(gk), _ptr(dq1), dq1.stride(0), _ptr(dk1), dk1.stride(0), _ptr(dgq), _ptr(dgk),
+                                         _ptr(ws), _stream()), 'segf_channel_gate_mix_bwd')
+    return dq1, dk1, dgq, dgk
+
+
+def _gated_mul_supported(dt, B, HW, Cc, ld):
+    return lib().segf_gated_mul_supported(dt, B * HW, Cc, ld)
+
+
+def gated_mul_fwd(a, v):
+    """z = a * v on [M, C] operands (any aligned row strides)."""
+    _need_cuda(a, v)
+    M, Cc = a.shape
+    _token_mixer_check('gated product', _gated_mul_supported, 1, M, Cc, a, v)
+    assert a.dtype == v.dtype and v.shape[1] == Cc
+    z = torch.empty((M, Cc), dtype=a.dtype, device=a.device)
+    _chk(lib().segf_gated_mul_fwd(dt_of(a), M, Cc, _ptr(a), a.stride(0), _ptr(v), v.stride(0), _ptr(z), z.stride(0), _stream()),
+         'segf_gated_mul_fwd')
+    return z
+
+
+def gated_mul_bwd(dz, a, v, da=None, dv=None):
+    """-> (da = dz * v, dv = dz * a), written into the given views when there are any."""
+    _need_cuda(dz, a, v)
+    M, Cc = a.shape
+    if da is None:
+        da = torch.empty((M, Cc), dtype=a.dtype, device=a.device)
+    if dv is None:
+        dv = torch.empty((M, Cc), dtype=a.dtype, device=a.device)
+    _token_mixer_check('gated product backward', _gated_mul_supported, 1, M, Cc, dz, a, v, da, dv)
+    assert dz.dtype == a.dtype == v.dtype == da.dtype == dv.dtype and v.shape[1] == Cc and dz.shape[1] == Cc
+    _chk(lib().segf_gated_mul_bwd(dt_of(a), M, Cc, _ptr(dz), dz.stride(0), _ptr(a), a.stride(0), _ptr(v), v.stride(0), _ptr(da),
+                                  da.stride(0), _ptr(dv), dv.stride(0), _stream()), 'segf_gated_mul_bwd')
+    return da, dv
+
+
 # ---- spatial ----------------------------------------------------------------------------------------
 def dwconv3x3_gelu_fwd(x, w9, bias, B, H, W, Cc, apply_gelu=True):
     y = torch.empty_like(x)
