@@ -423,6 +423,36 @@ int segf_gated_mul_fwd(int dt, int M, int C, const void* a, int64_t lda, const v
 int segf_gated_mul_bwd(int dt, int M, int C, const void* dz, int64_t lddz, const void* a, int64_t lda, const void* v, int64_t ldv,
                        void* da, int64_t ldda, void* dv, int64_t lddv, void* stream);
 
+/* ---- MetaFormer / ConvFormer (metaformer.py:198-241, 489-513; csrc/metaformer.hip): StarReLU and the residual scale, four streaming
+ * passes over token tensors [rows][cols] in the storage dtype with fp32 arithmetic, each result rounded once.
+ * Rules common to all of them (anything else returns SEGF_ERR_SHAPE before any launch, and the *_supported queries answer 0): rows > 0;
+ * cols % 8 == 0, 8 <= cols <= 8192 (StarReLU) or 2048 (residual scale); every leading dimension (elements between rows) >= cols with 16-byte
+ * aligned rows (ld % 8 == 0 for bf16, ld % 4 == 0 for fp32, base pointers 16-byte aligned) and rows * ld < 2^31, so an operand may be a
+ * column slice of a wider buffer; columns outside the slice are neither read nor written.  The *_supported queries answer for ONE leading dimension
+ * (ask once per operand).  *_blocks: workgroups of the launch = partial sums the backward adds.  Sums are
+ * per-workgroup partial sums in the caller's workspace (the *_ws queries: floats) added in a fixed order: no floating-point atomics, two
+ * runs give the same bits.  Nothing is allocated.
+ *
+ * StarReLU:  y = s * max(u, 0)^2 + b.  s and b are DEVICE pointers to one fp32 element each, read by the kernel (no host read, so the call
+ * can be captured in a graph).  Backward: du = dy * 2 s max(u, 0);  *ds = sum dy max(u, 0)^2 and *db = sum dy over all rows * cols
+ * elements in fp32 (lane -> wave -> workgroup partial -> one workgroup adds the partials); ds and db are independent pointers and may be
+ * adjacent floats. */
+int segf_starrelu_supported(int dt, int64_t rows, int cols, int64_t ld);
+int segf_starrelu_blocks(int64_t rows, int cols);
+int segf_starrelu_fwd(int dt, int64_t rows, int cols, const void* u, int64_t ldu, const float* s, const float* b, void* y, int64_t ldy,
+                      void* stream);
+int64_t segf_starrelu_bwd_ws(int64_t rows, int cols);
+int segf_starrelu_bwd(int dt, int64_t rows, int cols, const void* u, int64_t ldu, const void* dy, int64_t lddy, const float* s, void* du,
+                      int64_t lddu, float* ds, float* db, float* ws, void* stream);
+/* residual scale (Scale on the skip path, stages 3 and 4):  y = x * scale[c], scale fp32 [C], 16-byte aligned.
+ * Backward: dx = dy * scale[c];  dscale[c] = sum_rows dy * x (fp32 [C]; ws 16-byte aligned). */
+int segf_colscale_supported(int dt, int64_t rows, int C, int64_t ld);
+int segf_colscale_blocks(int64_t rows, int C);
+int segf_colscale_fwd(int dt, int64_t rows, int C, const void* x, int64_t ldx, const float* scale, void* y, int64_t ldy, void* stream);
+int64_t segf_colscale_bwd_ws(int64_t rows, int C);
+int segf_colscale_bwd(int dt, int64_t rows, int C, const void* dy, int64_t lddy, const void* x, int64_t ldx, const float* scale, void* dx,
+                      int64_t lddx, float* dscale, float* ws, void* stream);
+
 /* ---- depthwise 3x3 conv + bias + GELU(erf) on NHWC (mit.py:62-71,98-99 DWConv -> F.gelu) ----------- */
 int segf_dwconv3x3_gelu_fwd(int dt, int B, int H, int W, int C, const void* x, const float* w /*[C][9]*/,
                             const float* bias, int apply_gelu, void* y, void* stream);

@@ -11,7 +11,7 @@ from torch import nn
 
 from . import functional as Fh
 from .containers import (BatchNormWeights, ChannelsFirstLayerNormWeights, ConvWeights, LayerNormWeights, LinearWeights,
-                         init_mit_style)
+                         _no_forward, init_mit_style)
 
 # reference models/backbones/mit.py:149-156
 mit_settings = {
@@ -962,3 +962,208 @@ def rcvit_m(**kw):
 
 def rcvit_t(**kw):
     return RCViT(layers=[3, 3, 6, 3], embed_dims=[96, 128, 256, 512], **kw)
+
+
+# ---- MetaFormer / ConvFormer (models/backbones/metaformer.py) ------------------------------------------------------------------
+class _GainOnlyNorm(nn.Module):
+    """LayerNormGeneral(bias=False) / LayerNormWithoutBias (metaformer.py:299-370): a LayerNorm over the channels with a gain and no
+    bias, eps 1e-6.  State: `weight` alone.  It runs on the ordinary LayerNorm kernels fed a cached zero beta that is no parameter."""
+
+    def __init__(self, dim, eps=1e-6):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(dim))
+        self.eps = eps
+
+    forward = _no_forward
+
+
+_ZERO_BETA = {}
+
+
+def _zero_beta(C, device):
+    """fp32 zeros [C] on `device`, made once per (C, device) -- outside any captured region, because the first pass of a train step
+    is its warm-up -- and shared by every gain-only norm of that width.  Its gradient is discarded."""
+    key = (int(C), str(device))
+    z = _ZERO_BETA.get(key)
+    if z is None:
+        z = _ZERO_BETA[key] = torch.zeros(C, dtype=torch.float32, device=device)
+    return z
+
+
+class _StarReLUWeights(nn.Module):
+    """StarReLU's parameters (metaformer.py:224-241): scale [1] = 1, bias [1] = 0."""
+
+    def __init__(self):
+        super().__init__()
+        self.scale = nn.Parameter(torch.ones(1))
+        self.bias = nn.Parameter(torch.zeros(1))
+
+    forward = _no_forward
+
+
+class _ScaleWeights(nn.Module):
+    """Scale (metaformer.py:198-208): scale [dim]."""
+
+    def __init__(self, dim, init_value=1.0):
+        super().__init__()
+        self.scale = nn.Parameter(init_value * torch.ones(dim))
+
+    forward = _no_forward
+
+
+class _SepConv(nn.Module):
+    """metaformer.py:373-400: Linear (x2, no bias) -> StarReLU -> depthwise 7 x 7 (no bias) -> Linear (no bias)."""
+
+    def __init__(self, dim, expansion_ratio=2):
+        super().__init__()
+        med = int(expansion_ratio * dim)
+        self.pwconv1 = LinearWeights(dim, med, bias=False)
+        self.act1 = _StarReLUWeights()
+        self.dwconv = ConvWeights(med, med, 7, 1, 3, groups=med, bias=False)
+        self.pwconv2 = LinearWeights(med, dim, bias=False)
+
+
+class _MetaFormerMlp(nn.Module):
+    """metaformer.py:421-445 with drop = 0: Linear (x4, no bias) -> StarReLU -> Linear (no bias)."""
+
+    def __init__(self, dim, mlp_ratio=4):
+        super().__init__()
+        self.fc1 = LinearWeights(dim, int(mlp_ratio * dim), bias=False)
+        self.act = _StarReLUWeights()
+        self.fc2 = LinearWeights(int(mlp_ratio * dim), dim, bias=False)
+
+
+class _MlpHead(nn.Module):
+    """metaformer.py:448-468, the classification head the factories build and forward() never runs: parameters only, so that the
+    reference's checkpoints load strict."""
+
+    def __init__(self, dim, num_classes=1000, mlp_ratio=4):
+        super().__init__()
+        self.fc1 = LinearWeights(dim, int(mlp_ratio * dim))
+        self.norm = LayerNormWeights(int(mlp_ratio * dim))
+        self.fc2 = LinearWeights(int(mlp_ratio * dim), num_classes)
+
+
+class ConvFormerBlock(nn.Module):
+    """MetaFormerBlock (metaformer.py:471-513) with token_mixer = SepConv, gain-only norms, no drop path and no layer scale:
+    x = res_scale1(x) + SepConv(norm1(x));  x = res_scale2(x) + Mlp(norm2(x)).  res_scale{1,2} exist in stages 3 and 4 only.  The
+    residual add stays in the epilogue of the branch's last product; a scaled skip path is the product's `residual=` operand, and its
+    data gradient meets the branch's in the LayerNorm backward."""
+
+    def __init__(self, dim, res_scale_init_value=None):
+        super().__init__()
+        self.dim = dim
+        self.norm1 = _GainOnlyNorm(dim)
+        self.token_mixer = _SepConv(dim)
+        if res_scale_init_value:
+            self.res_scale1 = _ScaleWeights(dim, res_scale_init_value)
+        self.norm2 = _GainOnlyNorm(dim)
+        self.mlp = _MetaFormerMlp(dim)
+        if res_scale_init_value:
+            self.res_scale2 = _ScaleWeights(dim, res_scale_init_value)
+
+    def tokens(self, x, B, H, W):
+        zb = _zero_beta(self.dim, x.device)
+        tm, mlp = self.token_mixer, self.mlp
+        x, h = Fh.layer_norm_res(x, self.norm1.weight, zb, self.norm1.eps)
+        h = Fh.linear(h, tm.pwconv1.weight, None)
+        h = Fh.star_relu(h, tm.act1.scale, tm.act1.bias)
+        h = Fh.dwconv7x7(h, tm.dwconv.weight, None, B, H, W)
+        res = Fh.col_scale(x, self.res_scale1.scale) if hasattr(self, 'res_scale1') else x
+        x = Fh.linear(h, tm.pwconv2.weight, None, residual=res)
+        x, h = Fh.layer_norm_res(x, self.norm2.weight, zb, self.norm2.eps)
+        h = Fh.linear(h, mlp.fc1.weight, None)
+        h = Fh.star_relu(h, mlp.act.scale, mlp.act.bias)
+        res = Fh.col_scale(x, self.res_scale2.scale) if hasattr(self, 'res_scale2') else x
+        return Fh.linear(h, mlp.fc2.weight, None, residual=res)
+
+
+class _MetaFormerDownsampling(nn.Module):
+    """metaformer.py:172-195: [gain-only norm ->] conv (bias) [-> gain-only norm]; registration order pre_norm, conv, post_norm."""
+
+    def __init__(self, c1, c2, k, s, p, pre_norm=False, post_norm=False):
+        super().__init__()
+        if pre_norm:
+            self.pre_norm = _GainOnlyNorm(c1)
+        self.conv = ConvWeights(c1, c2, k, s, p)
+        if post_norm:
+            self.post_norm = _GainOnlyNorm(c2)
+
+
+class MetaFormer(nn.Module):
+    """models/backbones/metaformer.py:532-683 as the convformer_* factories build it: stem conv k7 s4 p2 (bias) + gain-only LayerNorm,
+    three [gain-only LayerNorm + conv k3 s2 p1 (bias)] downsamplers, four stages of ConvFormerBlocks with the residual scale (init 1.0)
+    in stages 3 and 4, and the four stage outputs without an output norm (forward_intermediates).  `norm` and `head` (MlpHead) are the
+    reference's unused classification tail: parameters that never receive a gradient.  No drop path (the factories pass no rate)."""
+
+    def __init__(self, depths, dims, res_scale_init_values=(None, None, 1.0, 1.0), num_classes=1000):
+        super().__init__()
+        from .containers import trunc_normal_
+        self.channels = list(dims)
+        self.depths = list(depths)
+        self.compute_dtype = torch.bfloat16
+        down = [3] + list(dims)
+        self.downsample_layers = nn.ModuleList(
+            [_MetaFormerDownsampling(down[0], down[1], 7, 4, 2, post_norm=True)] +
+            [_MetaFormerDownsampling(down[i], down[i + 1], 3, 2, 1, pre_norm=True) for i in range(1, 4)])
+        self.stages = nn.ModuleList(
+            [nn.Sequential(*[ConvFormerBlock(dims[i], res_scale_init_values[i]) for _ in range(depths[i])]) for i in range(4)])
+        self.norm = LayerNormWeights(dims[-1], eps=1e-6)
+        self.head = _MlpHead(dims[-1], num_classes)
+        for m in self.modules():                                # _init_weights (:632-636)
+            if isinstance(m, (nn.Conv2d, nn.Linear)):
+                trunc_normal_(m.weight, std=.02)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+
+    def forward_tokens(self, x):
+        """x: fp32 NCHW image.  Returns 4 TokenMaps (strides 4/8/16/32)."""
+        B, _, H, W = x.shape
+        outs = []
+        t = None
+        for i in range(4):
+            ds = self.downsample_layers[i]
+            if i == 0:
+                t = Fh.conv_patch(x, ds.conv.weight, ds.conv.bias, (B, H, W, 3, 7, 4, 2), image=True, dtype=self.compute_dtype)
+                H, W = (H + 4 - 7) // 4 + 1, (W + 4 - 7) // 4 + 1
+                t = Fh.layer_norm(t, ds.post_norm.weight, _zero_beta(self.channels[0], t.device), ds.post_norm.eps)
+            else:
+                t = Fh.layer_norm(t, ds.pre_norm.weight, _zero_beta(self.channels[i - 1], t.device), ds.pre_norm.eps)
+                t = Fh.conv_patch(t, ds.conv.weight, ds.conv.bias, (B, H, W, self.channels[i - 1], 3, 2, 1))
+                H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+            for blk in self.stages[i]:
+                t = blk.tokens(t, B, H, W)
+            if i < 3:
+                t, th = Fh.fork(t, 2)                # the stage output goes to the decode head and into the next downsampler's norm
+            else:
+                th = t
+            outs.append(TokenMap(th, B, H, W))
+        return outs
+
+    def forward(self, x):
+        return [tm.nchw() for tm in self.forward_tokens(x)]
+
+
+# the reference's ConvFormer factories (metaformer.py:926-1243); the suffixed names differ in their pretrained checkpoint alone
+CONVFORMER_SETTINGS = {
+    'convformer_s18': ([3, 3, 9, 3], [64, 128, 320, 512]),
+    'convformer_s36': ([3, 12, 18, 3], [64, 128, 320, 512]),
+    'convformer_m36': ([3, 12, 18, 3], [96, 192, 384, 576]),
+    'convformer_b36': ([3, 12, 18, 3], [128, 256, 512, 768]),
+}
+CONVFORMER_SUFFIXES = ('', '_384', '_in21ft1k', '_384_in21ft1k', '_in21k')
+
+
+def _convformer_factory(base):
+    depths, dims = CONVFORMER_SETTINGS[base]
+
+    def factory(**kw):
+        return MetaFormer(depths=depths, dims=dims, **kw)
+    return factory
+
+
+for _base in CONVFORMER_SETTINGS:
+    for _sfx in CONVFORMER_SUFFIXES:
+        globals()[_base + _sfx] = _convformer_factory(_base)
+        globals()[_base + _sfx].__name__ = _base + _sfx
+del _base, _sfx

@@ -22,12 +22,22 @@ backbone_registry.update({n: getattr(_backbones, n) for n in (
     'convnextv2_atto', 'convnextv2_femto', 'convnext_pico', 'convnextv2_nano', 'convnextv2_tiny', 'convnextv2_base',
     'convnextv2_large', 'convnextv2_huge', 'crossformer_tiny', 'crossformer_small', 'crossformer_base', 'crossformer_large',
     'rcvit_s', 'rcvit_m', 'rcvit_t')})
+backbone_registry.update({b + s: getattr(_backbones, b + s) for b in _backbones.CONVFORMER_SETTINGS for s in _backbones.CONVFORMER_SUFFIXES})
+_METAFORMER_UNBUILT = ('only the ConvFormer members of the MetaFormer family (models/backbones/metaformer.py) are built: convformer_s18, '
+                       'convformer_s36, convformer_m36, convformer_b36 and their _384 / _in21ft1k / _384_in21ft1k / _in21k aliases; '
+                       'attention (caformer), pooling (poolformerv2), identity and random token mixers have no kernels here')
 # names of the reference that are deliberately absent, and why (the KeyError says it)
-unavailable_backbones = {
+unavailable_backbones = {f'{fam}_{size}{sfx}': _METAFORMER_UNBUILT
+                         for fam, sizes, sfxs in (('caformer', ('s18', 's36', 'm36', 'b36'), _backbones.CONVFORMER_SUFFIXES),
+                                                  ('poolformerv2', ('s12', 's24', 's36', 'm36', 'm48'), ('',)),
+                                                  ('identityformer', ('s12', 's24', 's36', 'm36', 'm48'), ('',)),
+                                                  ('randformer', ('s12', 's24', 's36', 'm36', 'm48'), ('',)))
+                         for size in sizes for sfx in sfxs}
+unavailable_backbones.update({
     'rcvit_xs': 'its stage widths 56, 112 and 220 are outside the kernels\' channel rule (rows of 16-byte chunks: 220 is not a multiple '
                 'of 8, and the token-mixer kernels refuse it on the host; 56 and 112 are widths no GEMM or depthwise kernel of this '
                 'library is verified at); rcvit_s, rcvit_m and rcvit_t are available',
-}
+})
 head_dict = {'SegFormerHead': _heads.SegFormerHead, 'UPerHead': _heads.UPerHead, 'FPNHead': _heads.FPNHead}
 
 

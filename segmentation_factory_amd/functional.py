@@ -1209,6 +1209,58 @@ def gated_mul(a, v):
     return GatedMulFn.apply(a, v)
 
 
+# ---- MetaFormer / ConvFormer (metaformer.py:198-241, 489-513; csrc/metaformer.hip) ----------------------------------------------------
+@direct_grads(1, 2)
+class StarReLUFn(Function):
+    """s * relu(u)^2 + b with one-element learnable s and b (metaformer.py:224-241).  The kernels read s and b from device memory (no
+    host read: the call can be captured) and the backward writes the two whole-tensor sums into the parameters' flat-gradient views.
+    Kernel: starrelu_fwd_kernel / starrelu_bwd_kernel + starrelu_finalize_kernel."""
+
+    @staticmethod
+    def forward(ctx, u, scale, bias):
+        u = _rowmajor(u)
+        s, b = scale.detach().reshape(1), bias.detach().reshape(1)
+        ctx.save_for_backward(u, s)
+        ctx.pshapes = (scale.shape, bias.shape)
+        return hip.starrelu_fwd(u, s, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        u, s = ctx.saved_tensors
+        gs, gb = gslot(ctx, 1), gslot(ctx, 2)
+        du, ds, db = hip.starrelu_bwd(u, _rowmajor(dy), s, ds=gs.view(1) if gs is not None else None, db=gb.view(1) if gb is not None else None)
+        return du, ds.view(ctx.pshapes[0]), db.view(ctx.pshapes[1])
+
+
+def star_relu(u, scale, bias):
+    return StarReLUFn.apply(u, scale, bias)
+
+
+@direct_grads(1)
+class ColScaleFn(Function):
+    """x * scale[c] (Scale on the skip path of stages 3 and 4, metaformer.py:198-208, 501, 507).  Kernel: colscale_fwd_kernel /
+    colscale_bwd_kernel + colreduce_finalize."""
+
+    @staticmethod
+    def forward(ctx, x, scale):
+        x = _rowmajor(x)
+        sc = scale.detach().reshape(-1).contiguous()
+        ctx.save_for_backward(x, sc)
+        ctx.pshape = scale.shape
+        return hip.colscale_fwd(x, sc)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, sc = ctx.saved_tensors
+        gs = gslot(ctx, 1)
+        dx, dscale = hip.colscale_bwd(_rowmajor(dy), x, sc, dscale=gs.view(-1) if gs is not None and gs.is_contiguous() else None)
+        return dx, dscale.view(ctx.pshape)
+
+
+def col_scale(x, scale):
+    return ColScaleFn.apply(x, scale)
+
+
 @direct_grads(1, 2)
 class DWConvGeluFn(Function):
     """gelu(depthwise3x3(x) + b) on NHWC tokens (mit.py:62-71 + F.gelu at :99)."""

@@ -1165,6 +1165,90 @@ def gated_mul_bwd(dz, a, v, da=None, dv=None):
     return da, dv
 
 
+# ---- MetaFormer / ConvFormer: StarReLU and the residual scale (csrc/metaformer.hip) -----------------------------------------------
+def _metaformer_check(what, supported, rows, cols, limit, *ops):
+    """The refusal happens here, on the host, before any launch.  ops: the [rows, >= cols] operands that may be column slices."""
+    for t in ops:
+        assert t.ndim == 2 and t.shape[0] == rows and t.shape[1] >= cols and (t.stride(1) == 1 or t.shape[1] == 1), (what, tuple(t.shape))
+        assert t.dtype == ops[0].dtype, (what, t.dtype, ops[0].dtype)
+    lds = sorted({max(t.stride(0), cols) if rows == 1 else t.stride(0) for t in ops})
+    if not all(supported(dt_of(ops[0]), rows, cols, ld) for ld in lds):
+        raise RuntimeError(f'{what}: no kernel for {rows} rows of {cols} columns (leading dimensions {lds}): the column count must be a '
+                           f'multiple of 8 and at most {limit}, rows 16-byte aligned, rows * leading dimension below 2^31 '
+                           f'(there is no fallback path)')
+    for t in ops:
+        assert t.data_ptr() % 16 == 0, f'{what}: operand not 16-byte aligned'
+
+
+def _ld(t, cols):
+    return max(t.stride(0), cols) if t.shape[0] == 1 else t.stride(0)
+
+
+def _one_f32(t, what):
+    assert t.is_cuda and t.dtype == torch.float32 and t.numel() == 1, f'{what}: a one-element fp32 device tensor is expected'
+    return t
+
+
+def starrelu_fwd(u, s, b, y=None):
+    """y = s * relu(u)^2 + b on [rows, cols] (any aligned row stride); s, b: one-element fp32 device tensors, read by the kernel."""
+    _need_cuda(u, s, b)
+    rows, cols = u.shape
+    if y is None:
+        y = torch.empty((rows, cols), dtype=u.dtype, device=u.device)
+    _metaformer_check('StarReLU', lib().segf_starrelu_supported, rows, cols, 8192, u, y)
+    _chk(lib().segf_starrelu_fwd(dt_of(u), rows, cols, _ptr(u), _ld(u, cols), _ptr(_one_f32(s, 'StarReLU scale')),
+                                 _ptr(_one_f32(b, 'StarReLU bias')), _ptr(y), _ld(y, cols), _stream()), 'segf_starrelu_fwd')
+    return y
+
+
+def starrelu_bwd(u, dy, s, du=None, ds=None, db=None):
+    """-> (du = dy * 2 s relu(u), ds = sum dy relu(u)^2, db = sum dy); ds, db: fp32 [1] each (written into the given views when there are any)."""
+    _need_cuda(u, dy, s)
+    rows, cols = u.shape
+    if du is None:
+        du = torch.empty((rows, cols), dtype=u.dtype, device=u.device)
+    _metaformer_check('StarReLU backward', lib().segf_starrelu_supported, rows, cols, 8192, u, dy, du)
+    assert dy.shape[1] == cols
+    if ds is None:
+        ds = torch.empty(1, dtype=torch.float32, device=u.device)
+    if db is None:
+        db = torch.empty(1, dtype=torch.float32, device=u.device)
+    ws = _f32(lib().segf_starrelu_bwd_ws(rows, cols), u.device)
+    _chk(lib().segf_starrelu_bwd(dt_of(u), rows, cols, _ptr(u), _ld(u, cols), _ptr(dy), _ld(dy, cols), _ptr(_one_f32(s, 'StarReLU scale')),
+                                 _ptr(du), _ld(du, cols), _ptr(_one_f32(ds, 'ds')), _ptr(_one_f32(db, 'db')), _ptr(ws), _stream()),
+         'segf_starrelu_bwd')
+    return du, ds, db
+
+
+def colscale_fwd(x, scale, y=None):
+    """y = x * scale[c] on [rows, C] (any aligned row stride); scale fp32 [C]."""
+    _need_cuda(x, scale)
+    rows, Cc = x.shape[0], scale.numel()
+    if y is None:
+        y = torch.empty((rows, Cc), dtype=x.dtype, device=x.device)
+    _metaformer_check('residual scale', lib().segf_colscale_supported, rows, Cc, 2048, x, y)
+    assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.data_ptr() % 16 == 0
+    _chk(lib().segf_colscale_fwd(dt_of(x), rows, Cc, _ptr(x), _ld(x, Cc), _ptr(scale), _ptr(y), _ld(y, Cc), _stream()), 'segf_colscale_fwd')
+    return y
+
+
+def colscale_bwd(dy, x, scale, dx=None, dscale=None):
+    """-> (dx = dy * scale[c], dscale[c] = sum_rows dy * x fp32 [C]), written into the given views when there are any."""
+    _need_cuda(dy, x, scale)
+    rows, Cc = x.shape[0], scale.numel()
+    if dx is None:
+        dx = torch.empty((rows, Cc), dtype=x.dtype, device=x.device)
+    _metaformer_check('residual scale backward', lib().segf_colscale_supported, rows, Cc, 2048, dy, x, dx)
+    assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.data_ptr() % 16 == 0
+    if dscale is None:
+        dscale = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    assert dscale.dtype == torch.float32 and dscale.is_contiguous() and dscale.numel() == Cc
+    ws = _f32(lib().segf_colscale_bwd_ws(rows, Cc), x.device)
+    _chk(lib().segf_colscale_bwd(dt_of(x), rows, Cc, _ptr(dy), _ld(dy, Cc), _ptr(x), _ld(x, Cc), _ptr(scale), _ptr(dx), _ld(dx, Cc),
+                                 _ptr(dscale), _ptr(ws), _stream()), 'segf_colscale_bwd')
+    return dx, dscale
+
+
 # ---- spatial ----------------------------------------------------------------------------------------
 def dwconv3x3_gelu_fwd(x, w9, bias, B, H, W, Cc, apply_gelu=True):
     y = torch.empty_like(x)
