@@ -14,11 +14,16 @@ of the tensor; a dropped K element, a K slab counted twice, a truncating store o
 (entry point, kernel) pairs of the table that have no exact test: none (EXCLUDED is empty).
 
 Beside the table: products whose feature sizes N and K are one more and one less than a tile multiple (test_exact_feature_ragged_gemm),
-and the depthwise 7 x 7 / 3 x 3 convolutions, the bilinear resize by 2 / 4 / 8 and the column sum (test_exact_spatial_kernels).
+and the depthwise 7 x 7 / 3 x 3 convolutions, the bilinear resize by 2 / 4 / 8 and the column sum (test_exact_spatial_kernels).  The
+depthwise convolutions then run in EVERY form of csrc/conv.hip (strip, vertical walk with its row switch, one-launch; 3 x 3 forward
+included) at the shapes where their dispatch changes (test_exact_depthwise_forms, test_exact_depthwise7_shapes; the shape tables are those
+of tests/dwconv_refs.py), and one sampled 67 M-element map reaches the second strip of a dwconv7x7_kernel thread
+(test_exact_depthwise7_second_strip_of_a_thread).  Not covered for the depthwise family: the weight gradient at that size, the block caps
+of the three weight-gradient plans and the walk kernel's own grid-stride loop.
 
 Not covered by this module: kernels with a division or a transcendental.  Of those the norms and the column reductions (LayerNorm,
-BatchNorm, GRN, colsum) are checked against float64 in tests/test_norm_float64.py; GELU, softmax-CE and fp8 quantisation keep their
-tolerance tests, as do the bilinear backward / fused forms (bilinear_bwd, bilinear_bwd_248, upsample_add, fuse_map_248) and the pure data movers
+BatchNorm, GRN, colsum) are checked against float64 in tests/test_norm_float64.py, and GELU and its derivative inside the depthwise
+kernels in tests/test_dwconv_float64.py; softmax-CE and fp8 quantisation keep their tolerance tests, as do the bilinear backward / fused forms (bilinear_bwd, bilinear_bwd_248, upsample_add, fuse_map_248) and the pure data movers
 (im2col, col2im, permute021, nearest_up, cast2d), for which tests/exact_inputs.py has no reference yet.
 """
 import ctypes as C
@@ -934,6 +939,120 @@ def test_exact_spatial_kernels(dtype):
         X.assert_exact(out, X.bilinear_ref(xs64, B, h, w_, C_, h * r, w_ * r), f'bilinear x{r}')
     rows64 = X.lattice((70001, 40), g)
     X.assert_exact(hip.colsum(dev(rows64)), rows64.sum(0), 'colsum')
+
+
+def _depthwise_form_params():
+    """Every 3 x 3 shape of tests/dwconv_refs.py less (2, 32, 32, 64), both dtypes, every form that admits the shape."""
+    import dwconv_refs as D
+    out = []
+    for shape, _ in D.SHAPES3:
+        if shape == (2, 32, 32, 64):
+            continue
+        for dt, name in ((BF, 'bf16'), (F32, 'fp32')):
+            for form, rows in D.forms3(dict(shape=shape), dt, True):
+                out.append(pytest.param(shape, dt, form, rows, id=f'{"x".join(map(str, shape))}-{name}-{form}{f"-rows{rows}" if rows else ""}'))
+    return out
+
+
+def _lattice_rows(shape, g):
+    """Lattice activations as the float64 [B][H][W][C] map of the references and as their [rows][C] view."""
+    t = X.lattice(shape, g)
+    return t, t.reshape(-1, shape[-1])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('shape,dtype,form,rows', _depthwise_form_params())
+def test_exact_depthwise_forms(shape, dtype, form, rows, monkeypatch):
+    """The depthwise 3 x 3 WITHOUT the GELU on lattice inputs with integer bias, zero tolerance, in every form of csrc/conv.hip (strip,
+    vertical walk with its row switch, one-launch) at the shapes where the dispatch changes (tests/dwconv_refs.py SHAPES3): the forward
+    (strip and walk; the one-launch form has none) and dx, dw, db of the backward.  The form is forced with the existing switches and
+    asserted with hip.trace().  The references are the float64 slice sums of dwconv_refs: sums of small integers, exact in any order."""
+    import dwconv_refs as D
+    from segmentation_factory_amd import hip
+    B, H, W, C_ = shape
+    assert B * H * W < X.FP32_EXACT_TERMS                      # every dw / db sum stays exact in fp32
+    g = X.gen(71)
+    dev = lambda t, dt=dtype: t.to(dt).cuda().contiguous()                                # noqa: E731
+    (x4, x2), (dy4, dy2) = _lattice_rows(shape, g), _lattice_rows(shape, g)
+    w64, b64 = X.lattice((C_, 9), g), X.integers((C_,), g)
+    D.force_form(monkeypatch, form, rows)
+    if form != 'small':
+        with hip.trace() as t:
+            y = hip.dwconv3x3_gelu_fwd(dev(x2), dev(w64, F32), dev(b64, F32), B, H, W, C_, apply_gelu=False)
+        torch.cuda.synchronize()
+        D.assert_form_ran(t, form, dtype, False)
+        X.assert_exact(y, D.fwd_ref(x4, w64, b64, 3, False)['y'], f'dwconv3 {form} forward')
+    with hip.trace() as t:
+        dx, dw, db = hip.dwconv3x3_gelu_bwd(dev(x2), dev(w64, F32), dev(b64, F32), dev(dy2), B, H, W, C_, apply_gelu=False)
+    torch.cuda.synchronize()
+    D.assert_form_ran(t, form, dtype, True)
+    rdw, rdb, _, _ = D.wgrad_ref(x4, dy4, 3)
+    X.assert_exact(dx, D.dx_ref(dy4, w64, 3)[0], f'dwconv3 {form} dx')
+    X.assert_exact(dw, rdw, f'dwconv3 {form} dw')
+    X.assert_exact(db, rdb, f'dwconv3 {form} db')
+
+
+def _depthwise7_params():
+    import dwconv_refs as D
+    return [pytest.param(s, dt, id=f'{"x".join(map(str, s))}-{name}') for s, _ in D.SHAPES7 for dt, name in ((BF, 'bf16'), (F32, 'fp32'))]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('shape,dtype', _depthwise7_params())
+def test_exact_depthwise7_shapes(shape, dtype):
+    """The depthwise 7 x 7 forward (+ integer bias) and backward on lattice inputs at the shapes of tests/dwconv_refs.py SHAPES7: one pixel, a
+    map smaller than the kernel, strips whose last has one live pixel, two channel slabs in the weight gradient."""
+    import dwconv_refs as D
+    from segmentation_factory_amd import hip
+    B, H, W, C_ = shape
+    assert B * H * W < X.FP32_EXACT_TERMS
+    g = X.gen(72)
+    dev = lambda t, dt=dtype: t.to(dt).cuda().contiguous()                                # noqa: E731
+    (x4, x2), (dy4, dy2) = _lattice_rows(shape, g), _lattice_rows(shape, g)
+    w64, b64 = X.lattice((C_, 49), g), X.integers((C_,), g)
+    wt = dev(w64.t(), F32)
+    with hip.trace() as t:
+        y = hip.dwconv7x7_fwd(dev(x2), wt, dev(b64, F32), B, H, W, C_)
+        dx, dw, db = hip.dwconv7x7_bwd(dev(x2), wt, dev(dy2), B, H, W, C_)
+    torch.cuda.synchronize()
+    for n in ('dwconv7x7_kernel<T, false>', 'dwconv7x7_kernel<T, true>', 'dwconv7x7_wgrad_kernel<T>', 'dw7_scatter_kernel'):
+        assert any(n in k for k in t.kernels), (n, t.kernels)
+    rdw, rdb, _, _ = D.wgrad_ref(x4, dy4, 7)
+    X.assert_exact(y, D.fwd_ref(x4, w64, b64, 7, False)['y'], 'dwconv7 forward')
+    X.assert_exact(dx, D.dx_ref(dy4, w64, 7)[0], 'dwconv7 dx')
+    X.assert_exact(dw, rdw, 'dwconv7 dw')
+    X.assert_exact(db, rdb, 'dwconv7 db')
+
+
+@pytest.mark.gpu
+def test_exact_depthwise7_second_strip_of_a_thread():
+    """dwconv7x7_kernel runs more than one strip per thread only from about 67 M elements on (dw7_blocks: units * (C / 8) / 256 / 2048 >= 2),
+    which every ConvNeXt stage of the benchmark reaches and no other test does.  (8, 128, 128, 512) in bf16 on lattice inputs, forward
+    (+ integer bias) and dx: 2 strips per thread, asserted with the host arithmetic restated here.  Compared exactly on a sample -- 8192
+    pixels drawn with a fixed seed, the four corners and one full border row and column of the first and last image, all channels -- whose
+    float64 reference is gathered on the CPU for those pixels only, so the case costs no full-size float64 convolution.  The weight
+    gradient is left out at this size: it has no sampled form (every one of its 49 x 512 sums runs over all 131072 pixels, a full-size
+    reference), and its plan is covered by the small shapes of test_exact_depthwise7_shapes."""
+    import dwconv_refs as D
+    from segmentation_factory_amd import hip
+    B, H, W, C_ = 8, 128, 128, 512
+    units = B * H * ((W + 7) // 8)
+    assert min(4, max(1, units * (C_ // 8) // 256 // 2048)) == 2 == D.dw7_strips_per_thread(B, H, W, C_)
+    g = X.gen(73)
+    x8, dy8 = D.lattice_i8((B, H, W, C_), g), D.lattice_i8((B, H, W, C_), g)
+    w64, b64 = X.lattice((C_, 49), g), X.integers((C_,), g)
+    pix = D.sample_pixels(B, H, W, 8192, g)
+    rows = (pix[:, 0] * H + pix[:, 1]) * W + pix[:, 2]
+    wt = w64.t().float().cuda().contiguous()
+    xd, dyd = x8.reshape(-1, C_).to(BF).cuda(), dy8.reshape(-1, C_).to(BF).cuda()
+    with hip.trace() as t:
+        y = hip.dwconv7x7_fwd(xd, wt, b64.float().cuda(), B, H, W, C_)
+        dx, _, _ = hip.dwconv7x7_bwd(xd, wt, dyd, B, H, W, C_)
+    torch.cuda.synchronize()
+    assert any('dwconv7x7_kernel<T, false>' in k for k in t.kernels) and any('dwconv7x7_kernel<T, true>' in k for k in t.kernels), t.kernels
+    ys, dxs = y[rows.cuda()].cpu(), dx[rows.cuda()].cpu()
+    X.assert_exact(ys, D.gathered_conv7(x8, w64, b64, pix, 1), 'dwconv7 forward, second strip of a thread')
+    X.assert_exact(dxs, D.gathered_conv7(dy8, w64, None, pix, -1), 'dwconv7 dx, second strip of a thread')
 
 
 NEIGHBOURS = [0, 1, 4, 0, 2, 3, 0, 2, 2, 2, 2, 2, 2, 2, 2, 2, 1, 4, 4, 2, 2, 1, 1, 2, 1, 1, 1, 1, 1, 1, 2, 1, 1, 1, 1, 2, 0, 2, 1, 1, 1, 1, 2, 1,

@@ -5,7 +5,11 @@ by a standard deviation, NOT one that is wrong by a rounding, a dropped K elemen
 checks of the matrix and attention kernels (rounding of the stores, fp32 accumulation, every term counted once) are in
 tests/test_exact_kernels.py, and the norms and column reductions (LayerNorm, BatchNorm, GRN, colsum: a misplaced eps, n against n - 1, a
 dropped row, the paths that only large or ragged shapes reach) are held to the fp32 error of a float64 reference in
-tests/test_norm_float64.py."""
+tests/test_norm_float64.py.  The depthwise convolutions (for a 3 x 3 tap sum a dropped border tap is a ninth of one element's sum and
+passes here too) have their tight checks in tests/test_dwconv_float64.py -- every form (strip, walk, one-launch, Mix-FFN, deferred
+finalize, 7 x 7) against float64 under per-element derived bounds at the shapes where the dispatch changes -- and, on lattice inputs with
+zero tolerance, in tests/test_exact_kernels.py; test_dwconv3x3_gelu, test_dwconv7x7 and the form-against-form tests below stay as the
+coarse bar.  Not covered anywhere: the block caps of the depthwise weight-gradient plans and the walk kernel's own grid-stride loop."""
 import math
 import os
 
