@@ -47,6 +47,25 @@ def tokens_from_nchw(x, dtype):
     return TokenMap(t.reshape(B * H * W, C), B, H, W)
 
 
+def _drop_path_scales(owner, rates, per_block, B, device):
+    """Per block a tuple of `per_block` [B] rows of keep / kp scales (drop_path.py:18-25: x/kp*floor(kp+U)), all drawn as ONE
+    [n_draws, B] tensor per forward; Nones outside training and for blocks with rate 0, which use nn.Identity in the reference and draw
+    nothing.  owner.stochastic_override['drop_path'] (tests) replaces the draw with given keep flags [n_draws, B]."""
+    if not owner.training or all(r == 0 for r in rates):
+        return [(None,) * per_block] * len(rates)
+    draws = [r for r in rates if r > 0 for _ in range(per_block)]
+    if owner.stochastic_override is not None and 'drop_path' in owner.stochastic_override:
+        kp = 1.0 - torch.tensor(draws, dtype=torch.float32, device=device)[:, None]
+        scale = (owner.stochastic_override['drop_path'].to(device=device, dtype=torch.float32) / kp).contiguous()
+    else:
+        scale = Fh.stochastic_scales(owner, tuple(1.0 - r for r in draws), B, device)       # keep / kp, one row per draw
+    out, i = [], 0
+    for r in rates:
+        out.append(tuple(scale[i + j] for j in range(per_block)) if r > 0 else (None,) * per_block)
+        i += per_block if r > 0 else 0
+    return out
+
+
 class Attention(nn.Module):
     """Spatial-reduction attention (mit.py:9-59)."""
 
@@ -194,25 +213,8 @@ class MiT(nn.Module):
             cur += depths[s]
 
     def _drop_path_scales(self, B, device):
-        """One [n_draws, B] tensor of keep/kp scales per forward (drop_path.py:18-25: x/kp*floor(kp+U)); blocks
-        with rate 0 use nn.Identity in the reference and draw nothing."""
-        rates = [blk.drop_prob for s in range(4) for blk in getattr(self, f'block{s + 1}')]
-        if not self.training or all(r == 0 for r in rates):
-            return [(None, None)] * len(rates)
-        draws = [r for r in rates if r > 0 for _ in range(2)]
-        if self.stochastic_override is not None and 'drop_path' in self.stochastic_override:
-            kp = 1.0 - torch.tensor(draws, dtype=torch.float32, device=device)[:, None]
-            scale = (self.stochastic_override['drop_path'].to(device=device, dtype=torch.float32) / kp).contiguous()
-        else:
-            scale = Fh.stochastic_scales(self, tuple(1.0 - r for r in draws), B, device)       # keep / kp, one row per draw
-        out, i = [], 0
-        for r in rates:
-            if r > 0:
-                out.append((scale[i], scale[i + 1]))
-                i += 2
-            else:
-                out.append((None, None))
-        return out
+        """One (attention, mlp) pair of [B] keep / kp scale rows per block"""
+        return _drop_path_scales(self, [blk.drop_prob for s in range(4) for blk in getattr(self, f'block{s + 1}')], 2, B, device)
 
     def forward_tokens(self, x):
         """x: fp32 NCHW image.  Returns 4 TokenMaps (strides 4/8/16/32)."""
@@ -333,21 +335,8 @@ class _ConvNeXtBase(nn.Module):
         self.apply(_init_convnext)
 
     def _drop_path_scales(self, B, device):
-        """One keep/kp scale row per block with rate > 0 (drop_path.py:18-25; rate-0 blocks are nn.Identity)."""
-        rates = [blk.drop_prob for st in self.stages for blk in st]
-        if not self.training or all(r == 0 for r in rates):
-            return [None] * len(rates)
-        draws = [r for r in rates if r > 0]
-        if self.stochastic_override is not None and 'drop_path' in self.stochastic_override:
-            kp = 1.0 - torch.tensor(draws, dtype=torch.float32, device=device)[:, None]
-            scale = (self.stochastic_override['drop_path'].to(device=device, dtype=torch.float32) / kp).contiguous()
-        else:
-            scale = Fh.stochastic_scales(self, tuple(1.0 - r for r in draws), B, device)
-        out, i = [], 0
-        for r in rates:
-            out.append(scale[i] if r > 0 else None)
-            i += 1 if r > 0 else 0
-        return out
+        """One [B] keep / kp scale row per block"""
+        return [s for s, in _drop_path_scales(self, [blk.drop_prob for st in self.stages for blk in st], 1, B, device)]
 
     def forward_tokens(self, x):
         B, _, H, W = x.shape
@@ -726,25 +715,8 @@ class CrossFormer(nn.Module):
         return [blk for st in self.layers for blk in st.blocks]
 
     def _drop_path_scales(self, B, device):
-        """One (attention, mlp) pair of [B] keep / kp scale rows per block with rate > 0: the block's one DropPath module is applied
-        twice (:342-343); rate-0 blocks are nn.Identity in the reference and draw nothing."""
-        rates = [blk.drop_prob for blk in self._blocks()]
-        if not self.training or all(r == 0 for r in rates):
-            return [(None, None)] * len(rates)
-        draws = [r for r in rates if r > 0 for _ in range(2)]
-        if self.stochastic_override is not None and 'drop_path' in self.stochastic_override:
-            kp = 1.0 - torch.tensor(draws, dtype=torch.float32, device=device)[:, None]
-            scale = (self.stochastic_override['drop_path'].to(device=device, dtype=torch.float32) / kp).contiguous()
-        else:
-            scale = Fh.stochastic_scales(self, tuple(1.0 - r for r in draws), B, device)
-        out, i = [], 0
-        for r in rates:
-            if r > 0:
-                out.append((scale[i], scale[i + 1]))
-                i += 2
-            else:
-                out.append((None, None))
-        return out
+        """One (attention, mlp) pair of [B] keep / kp scale rows per block: the block's one DropPath module is applied twice (:342-343)"""
+        return _drop_path_scales(self, [blk.drop_prob for blk in self._blocks()], 2, B, device)
 
     def forward_tokens(self, x):
         """x: fp32 NCHW image.  Returns 4 TokenMaps (strides 4/8/16/32)."""

@@ -105,6 +105,24 @@ def derived_weight(param, kind, make):
     return t
 
 
+def _tap_major(weight, dtype, kind, device):
+    """The matrix [O][(ky,kx)][ci] of a convolution weight [O, Cin, kh, kw] in `dtype`, the operand of the products on im2col rows and of
+    the implicit 3x3 GEMMs, as the derived weight `kind`; -> [O, taps * Cin]."""
+    O, cin, taps = weight.shape[0], weight.shape[1], weight.shape[2] * weight.shape[3]
+    wsrc = weight.detach().contiguous()
+
+    def make():
+        t = torch.empty((O, taps, cin), dtype=dtype, device=device)
+        return t, [('perm', wsrc, t, O, cin, taps, cin)]
+    return derived_weight(wsrc, kind, make).view(O, taps * cin)
+
+
+def _tap_major_transposed(w, dtype):
+    """[ci][(ky,kx)][co] from the 3x3 parameter [O, I, 3, 3]: the weight matrix of the implicit GEMM that forms the data gradient."""
+    O, I = w.shape[0], w.shape[1]
+    return hip.permute021(w.reshape(1, O, I * 9), 1, O, I * 9, dtype).view(I, 9 * O)
+
+
 # ---- direct gradient placement ---------------------------------------------------------------------------------------------
 # When the fused optimizer has re-homed the parameters into one flat buffer and `enable_direct_grads()` was called (the
 # graphed train step does), every parameter carries `_segf_grad` = its fp32 view in the flat GRADIENT buffer.  The backward
@@ -183,40 +201,59 @@ def _flush_finalizes():
 _SCALED_DY = {}
 
 
-def _take_scaled(dy, rscale, rpg):
+def _park_scaled(dx, rscale, rpg):
+    """dx.scaled (the DropPath-scaled copy a fused LayerNorm backward wrote) waits in _SCALED_DY for the backward of x's producer."""
+    if getattr(dx, 'scaled', None) is not None:
+        if len(_SCALED_DY) > 64:
+            _SCALED_DY.clear()                   # (entries nobody came for: a consumer that did not need its input gradient)
+        _SCALED_DY[dx.data_ptr()] = (dx.scaled, rscale.data_ptr(), rpg, dx._version)
+        dx.scaled = None
+
+
+def _scaled_dy(dy, rscale, rpg):
+    """dy * rscale[row // rpg]: the copy parked by the LayerNorm backward that produced dy, when there was one, else a scale_rows launch."""
     hit = _SCALED_DY.pop(dy.data_ptr(), None)
     # hit[3]: dx's version when the entry was made.  The hand-over is only right while the tagged tensor has ONE consumer: a second
     # one makes autograd accumulate into dx in place (same address, version bumped) and the parked copy would be that of a partial sum
     if (hit is not None and hit[1] == rscale.data_ptr() and hit[2] == rpg and hit[0].shape == dy.shape and hit[0].dtype == dy.dtype
             and hit[3] == dy._version):
         return hit[0]
-    return None
+    return hip.scale_rows(dy, rscale, rpg)
+
+
+def _adjacent_slots(ctx, i, j):
+    """(slot of forward argument i, slot of j) when the two are ONE target in the flat gradient buffer, j's right behind i's, which a
+    two-stage column reduction writes in place and whose finalize may be deferred; None otherwise."""
+    a, b = gslot(ctx, i), gslot(ctx, j)
+    if a is None or b is None or not a.is_contiguous() or b.data_ptr() != a.data_ptr() + 4 * a.numel():
+        return None
+    return a, b
+
+
+def _queue_finalizes(ctx, *items):
+    """items: (the finalize item a kernel called with defer=True left, the forward-argument positions whose slots it fills), for the scope's
+    grouped finalize launch; the delivery callbacks of those slots fire at the flush."""
+    q = _FIN_QUEUE
+    for item, idx in items:
+        q.append((item, tuple(ctx._gslots[i] for i in idx)))
+    if len(q) >= FIN_QUEUE_MAX:
+        _flush_finalizes()
 
 
 def _ln_bwd(ctx, x, dy, g, mean, rstd, dy2=None, dres=None, dy2_patch=None):
     """LayerNorm backward with the (dgamma, dbeta) finalize deferred into the scope's grouped launch when both parameters carry adjacent
     flat-gradient slots; returns (dx, dgamma, dbeta) with None for gradients that will be delivered at the flush."""
-    gg, gb = gslot(ctx, 1), gslot(ctx, 2)
-    dgb = (gg, gb) if (gg is not None and gb is not None and gb.data_ptr() == gg.data_ptr() + 4 * gg.numel()) else None
+    dgb = _adjacent_slots(ctx, 1, 2)
     dp = getattr(ctx, 'dp', None)
     rscale, rpg = dp if dp is not None else (None, 1)
-    q = _FIN_QUEUE
-    if q is not None and dgb is not None:
-        slots = ctx._gslots
-        dx, item = hip.layernorm_bwd(x, dy, g, mean, rstd, dgb_out=dgb, dy2=dy2, dres=dres, defer=True, rscale=rscale, rows_per_group=rpg,
-                                     dy2_patch=dy2_patch)
-        q.append((item, (slots[1], slots[2])))
-        if len(q) >= FIN_QUEUE_MAX:
-            _flush_finalizes()
+    kw = dict(dgb_out=dgb, dy2=dy2, dres=dres, rscale=rscale, rows_per_group=rpg, dy2_patch=dy2_patch)
+    if _FIN_QUEUE is not None and dgb is not None:
+        dx, item = hip.layernorm_bwd(x, dy, g, mean, rstd, defer=True, **kw)
+        _queue_finalizes(ctx, (item, (1, 2)))
         out = (dx, None, None)
     else:
-        out = hip.layernorm_bwd(x, dy, g, mean, rstd, dgb_out=dgb, dy2=dy2, dres=dres, rscale=rscale, rows_per_group=rpg, dy2_patch=dy2_patch)
-    dx = out[0]
-    if getattr(dx, 'scaled', None) is not None:
-        if len(_SCALED_DY) > 64:
-            _SCALED_DY.clear()                   # (entries nobody came for: a consumer that did not need its input gradient)
-        _SCALED_DY[dx.data_ptr()] = (dx.scaled, rscale.data_ptr(), rpg, dx._version)
-        dx.scaled = None
+        out = hip.layernorm_bwd(x, dy, g, mean, rstd, **kw)
+    _park_scaled(out[0], rscale, rpg)
     return out
 
 
@@ -249,38 +286,65 @@ def defer_weight_grads():
         _SCALED_DY.clear()          # entries nobody collected must not outlive the backward they belong to (their addresses get reused)
 
 
-def _queue_dw(ctx, dy, x, n_out, n_in, tokens, iw=1, ib=2):
+def _queue_dw(ctx, dy, x, n_out, n_in, tokens, iw=1, ib=2, post_of=None):
     """Queue dW [n_out, n_in] = dy^T x and db = colsum(dy) of a Linear whose parameters (forward arguments iw, ib) both carry flat-gradient
-    slots; False when the product has to be issued by the caller (no scope, no slots)."""
+    slots; False when the product has to be issued by the caller (no scope, no slots).  post_of: the weight gradient needs a layout pass
+    behind the product, which then lands in a temporary [n_out, n_in] fp32 matrix, and the hip.prep_grouped job
+    post_of(temp, weight_slot) runs after the grouped launch."""
     q = _DW_QUEUE
     slots = getattr(ctx, '_gslots', None)
     if q is None or not slots or iw not in slots or ib not in slots:
         return False
-    gw, gb = slots[iw][0].view(n_out, n_in), slots[ib][0]
+    gw, gb = slots[iw][0], slots[ib][0]
     if gb.numel() != n_out or not gb.is_contiguous():
         return False
-    q.append(((dy, x, n_out, n_in, tokens, _splitk(n_out, n_in, tokens), gw, gb), (slots[iw], slots[ib]), None))
+    if post_of is None:
+        dst, post = gw.view(n_out, n_in), None
+    else:
+        dst = torch.empty((n_out, n_in), dtype=torch.float32, device=dy.device)
+        post = post_of(dst, gw)
+    q.append(((dy, x, n_out, n_in, tokens, _splitk(n_out, n_in, tokens), dst, gb), (slots[iw], slots[ib]), post))
     if len(q) >= DW_QUEUE_MAX:
         flush_weight_grads()
     return True
 
 
-def _queue_dw_post(ctx, dy, x, n_out, n_in, tokens, post_of):
-    """As _queue_dw for a layer whose weight gradient needs a layout pass behind the product: the product lands in a temporary
-    [n_out, n_in] fp32 matrix and the hip.prep_grouped job post_of(temp, weight_slot) runs after the grouped launch."""
-    q = _DW_QUEUE
-    slots = getattr(ctx, '_gslots', None)
-    if q is None or not slots or 1 not in slots or 2 not in slots:
-        return False
-    gb = slots[2][0]
-    if gb.numel() != n_out or not gb.is_contiguous():
-        return False
-    tmp = torch.empty((n_out, n_in), dtype=torch.float32, device=dy.device)
-    gw = slots[1][0]
-    q.append(((dy, x, n_out, n_in, tokens, _splitk(n_out, n_in, tokens), tmp, gb), (slots[1], slots[2]), post_of(tmp, gw)))
-    if len(q) >= DW_QUEUE_MAX:
-        flush_weight_grads()
-    return True
+def _from_tap_major(dwm, n_out, taps, cin, out=None):
+    """A convolution's weight gradient as its product leaves it, [O][(ky,kx)][ci] fp32, in the parameter's own [O][ci][(ky,kx)] layout;
+    out: the flat-gradient slot to write."""
+    return hip.permute021(dwm, n_out, taps, cin, torch.float32, out=out)
+
+
+def _linear_param_grads(ctx, dy, x, n_out, n_in, tokens, iw, ib, has_bias, wshape, taps=None):
+    """(dW, db) of a Linear-like layer y = x W^T + b whose weight and bias are the forward arguments iw, ib (ib None: no bias):
+    dW = dy^T x [n_out, n_in] in fp32, viewed as `wshape`, and db = colsum(dy), each None when it is not wanted -- or when it will be
+    delivered at the flush of defer_weight_grads().  Both wanted: queued for the scope's grouped launch where one is open and both
+    parameters carry flat-gradient slots (_queue_dw), else one pass over dy for both (hip.gemm_dw_db); only one: its own product or
+    column sum.  Whatever is issued here writes the parameter's flat-gradient slot where it has one.
+    taps: the layer is a convolution on an im2col matrix and the product comes out [n_out][taps][n_in / taps]: it lands in a temporary
+    and a layout pass (_from_tap_major, or its hip.prep_grouped job behind the grouped launch) writes the slot."""
+    need_w, need_b = ctx.needs_input_grad[iw], has_bias and ctx.needs_input_grad[ib]
+    gw, gb = gslot(ctx, iw), gslot(ctx, ib)
+    out = post_of = None
+    if taps is None:
+        out = gw.view(n_out, n_in) if gw is not None else None
+    else:
+        cin = n_in // taps
+        post_of = lambda t, g: ('perm', t, g, n_out, taps, cin, taps)       # noqa: E731
+    dw = db = None
+    if need_w and need_b:
+        if _queue_dw(ctx, dy, x, n_out, n_in, tokens, iw, ib, post_of):           # deferred + grouped under defer_weight_grads(); else right here
+            return None, None
+        dw, db = hip.gemm_dw_db(dy, x, n_out, n_in, tokens, split_k=_splitk(n_out, n_in, tokens), out=out, db_out=gb)   # one pass over dy for both
+    elif need_w:
+        dw = hip.gemm(2, dy, x, n_out, n_in, tokens, out=out, out_dtype=torch.float32, split_k=_splitk(n_out, n_in, tokens))
+    elif need_b:
+        db = hip.colsum(dy, out=gb)
+    if dw is not None:
+        if taps is not None:
+            dw = _from_tap_major(dw, n_out, taps, cin, out=gw)
+        dw = dw.view(wshape)
+    return dw, db
 
 
 def direct_grads(*param_idx):
@@ -421,24 +485,9 @@ class LinearFn(Function):
                     db = hip.colsum(dyp)[:N]
             return dx, dw, db, None, None, None, None, None
         wv = w[:N] if Np > N else w
-        dys = dy
-        if rscale is not None:
-            dys = _take_scaled(dy, rscale, rpg)              # written by the LayerNorm backward that produced dy, when there was one
-            if dys is None:
-                dys = hip.scale_rows(dy, rscale, rpg)
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = hip.gemm(1, dys, wv, M, K, N)
-        gw, gb = gslot(ctx, 1, (N, K)), gslot(ctx, 2)       # flat-gradient views (direct placement) or None
-        if ctx.needs_input_grad[1] and has_bias and ctx.needs_input_grad[2]:
-            if not _queue_dw(ctx, dys, x, N, K, M):           # deferred + grouped under defer_weight_grads(); else right here
-                dw, db = hip.gemm_dw_db(dys, x, N, K, M, split_k=_splitk(N, K, M), out=gw, db_out=gb)   # one pass over dy for both
-                dw = dw.view(wshape)
-        else:
-            if ctx.needs_input_grad[1]:
-                dw = hip.gemm(2, dys, x, N, K, M, out=gw, out_dtype=torch.float32, split_k=_splitk(N, K, M)).view(wshape)
-            if has_bias and ctx.needs_input_grad[2]:
-                db = hip.colsum(dys, out=gb)
+        dys = _scaled_dy(dy, rscale, rpg) if rscale is not None else dy
+        dx = hip.gemm(1, dys, wv, M, K, N) if ctx.needs_input_grad[0] else None
+        dw, db = _linear_param_grads(ctx, dys, x, N, K, M, 1, 2, has_bias, wshape)
         dres = dy if (has_res and ctx.needs_input_grad[3]) else None
         return dx, dw, db, dres, None, None, None, None
 
@@ -500,19 +549,10 @@ class LinearForkFn(Function):
         x, w = ctx.saved_tensors
         M, N, K, has_bias, wshape = ctx.meta
         dy = _rowmajor(dy)
-        dx = dw = db = None
+        dx = None
         if ctx.needs_input_grad[0]:
             dx = hip.gemm(1, dy, w, M, K, N, residual=_rowmajor(dx2) if dx2 is not None else None)
-        gw, gb = gslot(ctx, 1, (N, K)), gslot(ctx, 2)
-        if ctx.needs_input_grad[1] and has_bias and ctx.needs_input_grad[2]:
-            if not _queue_dw(ctx, dy, x, N, K, M):
-                dw, db = hip.gemm_dw_db(dy, x, N, K, M, split_k=_splitk(N, K, M), out=gw, db_out=gb)
-                dw = dw.view(wshape)
-        else:
-            if ctx.needs_input_grad[1]:
-                dw = hip.gemm(2, dy, x, N, K, M, out=gw, out_dtype=torch.float32, split_k=_splitk(N, K, M)).view(wshape)
-            if has_bias and ctx.needs_input_grad[2]:
-                db = hip.colsum(dy, out=gb)
+        dw, db = _linear_param_grads(ctx, dy, x, N, K, M, 1, 2, has_bias, wshape)
         return dx, dw, db
 
 
@@ -528,15 +568,23 @@ def linear(x, weight, bias=None, residual=None, rscale=None, rows_per_group=None
     return y
 
 
+def _ln_enter(ctx, x, gamma, beta, dp_scale, dp_rpg, patch=None):
+    """Forward entry of the LayerNorm family: ctx.dp = the DropPath hand-over of x's producer (_dp_of) for the backward, ctx.patch = the
+    (log2 W, log2 sr) of a patch-major second output; -> (x, gamma, beta) as the kernels take them."""
+    ctx.dp = (dp_scale, int(dp_rpg)) if dp_scale is not None else None
+    if patch is not None:
+        ctx.patch = (int(patch[0]), int(patch[1]))
+    x = x if x.is_contiguous() else x.contiguous()
+    return x, gamma.detach().contiguous(), beta.detach().contiguous()
+
+
 @direct_grads(1, 2)
 class LayerNormFn(Function):
     """nn.LayerNorm over the channel dim of token rows (mit.py:107,136-140; convnext.py:8-23 in NHWC)."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, dp_scale=None, dp_rpg=1):
-        ctx.dp = (dp_scale, int(dp_rpg)) if dp_scale is not None else None
-        x = x if x.is_contiguous() else x.contiguous()
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        x, g, b = _ln_enter(ctx, x, gamma, beta, dp_scale, dp_rpg)
         y, mean, rstd = hip.layernorm_fwd(x, g, b, eps)
         ctx.save_for_backward(x, g, mean, rstd)
         return y
@@ -567,9 +615,7 @@ class LayerNormResFn(Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, dp_scale=None, dp_rpg=1):
-        ctx.dp = (dp_scale, int(dp_rpg)) if dp_scale is not None else None
-        x = x if x.is_contiguous() else x.contiguous()
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        x, g, b = _ln_enter(ctx, x, gamma, beta, dp_scale, dp_rpg)
         y, mean, rstd = hip.layernorm_fwd(x, g, b, eps)
         ctx.save_for_backward(x, g, mean, rstd)
         return x.view_as(x), y
@@ -598,38 +644,22 @@ def _ln_linear_fwd_fused(x, g, b, w, bias):
             and all(t.data_ptr() % 16 == 0 for t in (x, g, b, w)) and bias.data_ptr() % 4 == 0)
 
 
-def _park_scaled(dx, rscale, rpg):
-    """dx.scaled (the DropPath-scaled copy a fused LayerNorm backward wrote) waits in _SCALED_DY for the backward of x's producer."""
-    if getattr(dx, 'scaled', None) is not None:
-        if len(_SCALED_DY) > 64:
-            _SCALED_DY.clear()
-        _SCALED_DY[dx.data_ptr()] = (dx.scaled, rscale.data_ptr(), rpg, dx._version)
-        dx.scaled = None
-
-
 def _ln_linear_bwd(ctx, dh, dres, x, g, b, mean, rstd, y, w, iw, ib, dy2=None, dy2_patch=None):
     """hip.layernorm_linear_bwd for a formula whose forward arguments 1, 2 are the norm's parameters and iw, ib the Linear's: the four
     parameter gradients written in place / deferred into the scope's grouped finalize where all four carry flat-gradient slots.
     -> (dx, dgamma, dbeta, dw, dbias) with None for gradients that are delivered at the flush."""
     N, K = w.shape
     rscale, rpg = ctx.dp if ctx.dp is not None else (None, 1)
-    gg, gb, gw, gb1 = gslot(ctx, 1), gslot(ctx, 2), gslot(ctx, iw), gslot(ctx, ib)
+    dgb, gw, gb1 = _adjacent_slots(ctx, 1, 2), gslot(ctx, iw), gslot(ctx, ib)
     outs = None
-    if (gg is not None and gb is not None and gw is not None and gb1 is not None and gb.data_ptr() == gg.data_ptr() + 4 * gg.numel()
-            and gw.is_contiguous() and gb1.is_contiguous()):
-        outs = (gw.view(N, K), gb1, gg, gb)
+    if dgb is not None and gw is not None and gb1 is not None and gw.is_contiguous() and gb1.is_contiguous():
+        outs = (gw.view(N, K), gb1, *dgb)
     kw = dict(dres=dres, rscale=rscale, rows_per_group=rpg, outs=outs)
     if y is None:
         kw.update(beta=b, dy2=dy2, dy2_patch=dy2_patch)
-    q = _FIN_QUEUE
-    if q is not None and outs is not None:
-        slots = ctx._gslots
+    if _FIN_QUEUE is not None and outs is not None:
         dx, items = hip.layernorm_linear_bwd(dh, w, x, y, g, mean, rstd, defer=True, **kw)
-        q.append((items[0], (slots[iw],)))
-        q.append((items[1], (slots[ib],)))
-        q.append((items[2], (slots[1], slots[2])))
-        if len(q) >= FIN_QUEUE_MAX:
-            _flush_finalizes()
+        _queue_finalizes(ctx, (items[0], (iw,)), (items[1], (ib,)), (items[2], (1, 2)))
         res = (dx, None, None, None, None)
     else:
         dx, dw, db1, dg, db = hip.layernorm_linear_bwd(dh, w, x, y, g, mean, rstd, **kw)
@@ -650,9 +680,7 @@ class LayerNormResLinearFn(Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, weight, bias, dp_scale=None, dp_rpg=1):
-        ctx.dp = (dp_scale, int(dp_rpg)) if dp_scale is not None else None
-        x = x if x.is_contiguous() else x.contiguous()
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        x, g, b = _ln_enter(ctx, x, gamma, beta, dp_scale, dp_rpg)
         M, K = x.shape
         N = weight.shape[0]
         w = _w(weight.reshape(N, -1), x.dtype)
@@ -677,14 +705,18 @@ class LayerNormResLinearFn(Function):
         return dx, dg, db, None, dw, db1, None, None
 
 
+def _ln_linear_trained(x, gamma, beta, weight, bias):
+    """The part the LayerNorm + Linear formulas' *_ok rules share: a bf16 training pass on the device, all four parameters present and
+    trained."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.ndim == 2 and torch.is_grad_enabled() and x.requires_grad):
+        return False
+    return bias is not None and weight.ndim == 2 and all(p.requires_grad for p in (gamma, beta, weight, bias))
+
+
 def layer_norm_res_linear_ok(x, gamma, beta, weight, bias):
     """May (x, Linear(LayerNorm(x))) run as LayerNormResLinearFn?  The library's shape / size / policy rule
     (segf_layernorm_linear_bwd_supported), a training pass, and all four parameters present and trained."""
-    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.ndim == 2 and torch.is_grad_enabled() and x.requires_grad):
-        return False
-    if bias is None or weight.ndim != 2 or not all(p.requires_grad for p in (gamma, beta, weight, bias)):
-        return False
-    return hip.layernorm_linear_bwd_supported(x.dtype, x.shape[0], x.shape[1], weight.shape[0])
+    return _ln_linear_trained(x, gamma, beta, weight, bias) and hip.layernorm_linear_bwd_supported(x.dtype, x.shape[0], x.shape[1], weight.shape[0])
 
 
 def layer_norm_res_linear(x, gamma, beta, eps, weight, bias):
@@ -705,10 +737,7 @@ class LayerNormResPatchFn(Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, lw, ls, dp_scale=None, dp_rpg=1):
-        ctx.dp = (dp_scale, int(dp_rpg)) if dp_scale is not None else None
-        ctx.patch = (int(lw), int(ls))
-        x = x if x.is_contiguous() else x.contiguous()
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        x, g, b = _ln_enter(ctx, x, gamma, beta, dp_scale, dp_rpg, patch=(lw, ls))
         y, mean, rstd, col = hip.layernorm_fwd(x, g, b, eps, patch=ctx.patch)
         ctx.save_for_backward(x, g, mean, rstd)
         return x.view_as(x), y, col
@@ -741,10 +770,7 @@ class LayerNormResPatchLinearFn(Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, lw, ls, weight, bias, dp_scale=None, dp_rpg=1):
-        ctx.dp = (dp_scale, int(dp_rpg)) if dp_scale is not None else None
-        ctx.patch = (int(lw), int(ls))
-        x = x if x.is_contiguous() else x.contiguous()
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        x, g, b = _ln_enter(ctx, x, gamma, beta, dp_scale, dp_rpg, patch=(lw, ls))
         M, K = x.shape
         N = weight.shape[0]
         w = _w(weight.reshape(N, -1), x.dtype)
@@ -780,10 +806,7 @@ class LayerNormResPatchLinearFn(Function):
         M, K = x.shape
         N = w.shape[0]
         dy = hip.gemm(1, dq, w, M, K, N)
-        dw = dbq = None
-        if not _queue_dw(ctx, dq, y, N, K, M, 6, 7):
-            dw, dbq = hip.gemm_dw_db(dq, y, N, K, M, split_k=_splitk(N, K, M), out=gslot(ctx, 6, (N, K)), db_out=gslot(ctx, 7))
-            dw = dw.view(ctx.wshape)
+        dw, dbq = _linear_param_grads(ctx, dq, y, N, K, M, 6, 7, True, ctx.wshape)
         dx, dg, db = _ln_bwd(ctx, x, dy, g, mean, rstd, dy2=dcol, dres=dres, dy2_patch=patch)
         return dx, dg, db, None, None, None, dw, dbq, None, None
 
@@ -791,11 +814,7 @@ class LayerNormResPatchLinearFn(Function):
 def layer_norm_res_patch_linear_ok(x, gamma, beta, weight, bias):
     """May (x, Linear(LayerNorm(x)), col) run as LayerNormResPatchLinearFn?  The library's rule for the one-pass forward
     (segf_layernorm_linear_fwd_supported), a training pass, and all four parameters present and trained."""
-    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.ndim == 2 and torch.is_grad_enabled() and x.requires_grad):
-        return False
-    if bias is None or weight.ndim != 2 or not all(p.requires_grad for p in (gamma, beta, weight, bias)):
-        return False
-    return hip.layernorm_linear_fwd_supported(x.dtype, x.shape[0], x.shape[1], weight.shape[0])
+    return _ln_linear_trained(x, gamma, beta, weight, bias) and hip.layernorm_linear_fwd_supported(x.dtype, x.shape[0], x.shape[1], weight.shape[0])
 
 
 def layer_norm_res_patch_linear(x, gamma, beta, eps, W, sr, weight, bias):
@@ -826,13 +845,7 @@ class ConvFromColFn(Function):
         M, K = col.shape
         O, Cin = weight.shape[0], weight.shape[1]
         assert K == k * k * Cin
-        dtype = col.dtype
-        wsrc = weight.detach().contiguous()
-
-        def make_wmat():
-            t = torch.empty((O, k * k, Cin), dtype=dtype, device=col.device)
-            return t, [('perm', wsrc, t, O, Cin, k * k, Cin)]
-        wmat = derived_weight(wsrc, ('patch', dtype, K), make_wmat).view(O, K)                 # [O][(ky,kx)][ci]
+        wmat = _tap_major(weight, col.dtype, ('patch', col.dtype, K), col.device)
         y = hip.gemm(0, col, wmat, M, O, K, bias=bias.detach() if bias is not None else None)
         ctx.save_for_backward(col, wmat)
         ctx.meta = (M, O, K, k, Cin, bias is not None, weight.shape)
@@ -843,20 +856,8 @@ class ConvFromColFn(Function):
         col, wmat = ctx.saved_tensors
         M, O, K, k, Cin, has_bias, wshape = ctx.meta
         dy = _rowmajor(dy)
-        dcol = dw = db = None
-        gw, gb = gslot(ctx, 1), gslot(ctx, 2)
-        if ctx.needs_input_grad[1] and has_bias and ctx.needs_input_grad[2]:
-            if not (gw is not None and _queue_dw_post(ctx, dy, col, O, K, M, lambda t, g: ('perm', t, g, O, k * k, Cin, k * k))):
-                dwm, db = hip.gemm_dw_db(dy, col, O, K, M, split_k=_splitk(O, K, M), db_out=gb)           # [O][(ky,kx)][ci]
-                dw = hip.permute021(dwm, O, k * k, Cin, torch.float32, out=gw).view(wshape)
-        else:
-            if ctx.needs_input_grad[1]:
-                dwm = hip.gemm(2, dy, col, O, K, M, out_dtype=torch.float32, split_k=_splitk(O, K, M))
-                dw = hip.permute021(dwm, O, k * k, Cin, torch.float32, out=gw).view(wshape)
-            if has_bias and ctx.needs_input_grad[2]:
-                db = hip.colsum(dy, out=gb)
-        if ctx.needs_input_grad[0]:
-            dcol = hip.gemm(1, dy, wmat, M, K, O)
+        dw, db = _linear_param_grads(ctx, dy, col, O, K, M, 1, 2, has_bias, wshape, taps=k * k)
+        dcol = hip.gemm(1, dy, wmat, M, K, O) if ctx.needs_input_grad[0] else None
         return dcol, dw, db, None
 
 
@@ -871,9 +872,7 @@ class LayerNormForkFn(Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, dp_scale=None, dp_rpg=1):
-        ctx.dp = (dp_scale, int(dp_rpg)) if dp_scale is not None else None
-        x = x if x.is_contiguous() else x.contiguous()
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        x, g, b = _ln_enter(ctx, x, gamma, beta, dp_scale, dp_rpg)
         y, mean, rstd = hip.layernorm_fwd(x, g, b, eps)
         ctx.save_for_backward(x, g, mean, rstd)
         return y, y.view_as(y)
@@ -959,9 +958,10 @@ class ConvPatchFn(Function):
             ld = 160
         x = x if x.is_contiguous() else x.contiguous()
         col = hip.im2col(x, dtype, image, B, H, W, Cin, k, k, stride, pad, Ho, Wo, ld)
-        wsrc = weight.detach().contiguous()
         b = bias.detach() if bias is not None else None
         if stream_form:
+            wsrc = weight.detach().contiguous()
+
             def make_wpad():                             # rows of [(ky,kx)][ci] at a row stride of `ld`, the pad columns zero
                 t = torch.empty((O, ld), dtype=dtype, device=x.device)
                 return t, [('perm', wsrc, t, O, Cin, k * k, Cin, ld), ('zero', t[:, K:])]
@@ -969,10 +969,7 @@ class ConvPatchFn(Function):
             wmat = wpad[:, :K]
             y = hip.gemm(0, col, wpad, B * Ho * Wo, O, ld, bias=b)
         else:
-            def make_wmat():
-                t = torch.empty((O, k * k, Cin), dtype=dtype, device=x.device)
-                return t, [('perm', wsrc, t, O, Cin, k * k, Cin)]
-            wmat = derived_weight(wsrc, ('patch', dtype, K), make_wmat).view(O, K)             # [O][(ky,kx)][ci]
+            wmat = _tap_major(weight, dtype, ('patch', dtype, K), x.device)
             y = hip.gemm(0, col, wmat, B * Ho * Wo, O, K, bias=b)
         # the im2col matrix itself is kept for the weight gradient (k*k/stride^2 <= 3.1x the conv input, < 1 GB in total
         # for SegFormer-B0 at batch 64 out of 288 GB): rebuilding it in backward costs a second pass over the image
@@ -987,18 +984,8 @@ class ConvPatchFn(Function):
         B, H, W, Cin, k, stride, pad = geom
         M = B * Ho * Wo
         dy = _rowmajor(dy)
-        dx = dw = db = None
-        gw, gb = gslot(ctx, 1), gslot(ctx, 2)                # flat-gradient views: the permute / column sum write in place
-        if ctx.needs_input_grad[1] and has_bias and ctx.needs_input_grad[2]:
-            if not (gw is not None and _queue_dw_post(ctx, dy, col, O, K, M, lambda t, g: ('perm', t, g, O, k * k, Cin, k * k))):
-                dwm, db = hip.gemm_dw_db(dy, col, O, K, M, split_k=_splitk(O, K, M), db_out=gb)           # [O][(ky,kx)][ci]
-                dw = hip.permute021(dwm, O, k * k, Cin, torch.float32, out=gw).view(wshape)
-        else:
-            if ctx.needs_input_grad[1]:
-                dwm = hip.gemm(2, dy, col, O, K, M, out_dtype=torch.float32, split_k=_splitk(O, K, M))
-                dw = hip.permute021(dwm, O, k * k, Cin, torch.float32, out=gw).view(wshape)
-            if has_bias and ctx.needs_input_grad[2]:
-                db = hip.colsum(dy, out=gb)
+        dx = None
+        dw, db = _linear_param_grads(ctx, dy, col, O, K, M, 1, 2, has_bias, wshape, taps=k * k)
         if ctx.needs_input_grad[0] and not image:
             dcol = hip.gemm(1, dy, wmat, M, K, O)
             dx = hip.col2im(dcol, B, H, W, Cin, k, k, stride, pad, Ho, Wo)
@@ -1124,9 +1111,7 @@ class QkvSplit3Fn(Function):
             jobs.append(('cast', _rowmajor(d), sl) if d is not None else ('zero', sl))
         hip.prep_grouped(jobs)
         dx = hip.gemm(1, dqkv, w, M, K, N) if ctx.needs_input_grad[0] else None
-        dw = None
-        if ctx.needs_input_grad[1]:
-            dw = hip.gemm(2, dqkv, x, N, K, M, out=gslot(ctx, 1, (N, K)), out_dtype=torch.float32, split_k=_splitk(N, K, M)).view(wshape)
+        dw, _ = _linear_param_grads(ctx, dqkv, x, N, K, M, 1, None, False, wshape)
         return dx, dw
 
 
@@ -1282,14 +1267,10 @@ class DWConvGeluFn(Function):
         B, H, W, Cc, apply_gelu, wshape = ctx.meta
         dy = dy if dy.is_contiguous() else dy.contiguous()
         gw, gb = gslot(ctx, 1), (gslot(ctx, 2) if b is not None else None)       # flat-gradient views: written in place, no copy
-        q = _FIN_QUEUE
-        if q is not None and gw is not None and gb is not None and gb.data_ptr() == gw.data_ptr() + 4 * gw.numel() and gw.is_contiguous():
+        if _FIN_QUEUE is not None and _adjacent_slots(ctx, 1, 2) is not None:
             # the finalize of the (dw, db) partial sums joins the step's grouped finalize launches (one instead of two launches per block)
-            slots = ctx._gslots
             dx, item = hip.dwconv3x3_gelu_bwd(x, w9, b, dy, B, H, W, Cc, apply_gelu, dw_out=gw, db_out=gb, defer=True)
-            q.append((item, (slots[1], slots[2])))
-            if len(q) >= FIN_QUEUE_MAX:
-                _flush_finalizes()
+            _queue_finalizes(ctx, (item, (1, 2)))
             return dx, None, None, None, None, None, None
         dx, dw, db = hip.dwconv3x3_gelu_bwd(x, w9, b, dy, B, H, W, Cc, apply_gelu, dw_out=gw, db_out=gb)
         return dx, dw.view(wshape), (db if b is not None else None), None, None, None, None
@@ -1328,24 +1309,13 @@ class DWConvGeluLinearFn(Function):
         x, w9, b, g, w2, rscale = ctx.saved_tensors
         B, H, W, Cc, N, M, wshape, w2shape, has_res = ctx.meta
         dy = _rowmajor(dy)
-        dys = dy
-        if rscale is not None:
-            dys = _take_scaled(dy, rscale, H * W)              # written by the LayerNorm backward that produced dy, when there was one
-            if dys is None:
-                dys = hip.scale_rows(dy, rscale, H * W)
-        dw2 = db2 = None
-        if not _queue_dw(ctx, dys, g, N, Cc, M):
-            dw2, db2 = hip.gemm_dw_db(dys, g, N, Cc, M, split_k=_splitk(N, Cc, M), out=gslot(ctx, 1, (N, Cc)), db_out=gslot(ctx, 2))
-            dw2 = dw2.view(w2shape)
+        dys = _scaled_dy(dy, rscale, H * W) if rscale is not None else dy
+        dw2, db2 = _linear_param_grads(ctx, dys, g, N, Cc, M, 1, 2, True, w2shape)
         gw, gb = gslot(ctx, 3), gslot(ctx, 4)
         dres = dy if (has_res and ctx.needs_input_grad[8]) else None
-        q = _FIN_QUEUE
-        if q is not None and gw is not None and gb is not None and gb.data_ptr() == gw.data_ptr() + 4 * gw.numel() and gw.is_contiguous():
-            slots = ctx._gslots
+        if _FIN_QUEUE is not None and _adjacent_slots(ctx, 3, 4) is not None:
             dx, item = hip.dwconv3x3_gelu_bwd_fc2(x, w9, b, dys, w2, B, H, W, Cc, N, dw_out=gw, db_out=gb, defer=True)
-            q.append((item, (slots[3], slots[4])))
-            if len(q) >= FIN_QUEUE_MAX:
-                _flush_finalizes()
+            _queue_finalizes(ctx, (item, (3, 4)))
             return dx, dw2, db2, None, None, None, None, None, dres, None
         dx, dw, db = hip.dwconv3x3_gelu_bwd_fc2(x, w9, b, dys, w2, B, H, W, Cc, N, dw_out=gw, db_out=gb)
         return dx, dw2, db2, dw.view(wshape), db, None, None, None, dres, None
@@ -1368,6 +1338,17 @@ def dwconv3x3_gelu_linear(x, weight2, bias2, weight, bias, B, H, W, residual=Non
     return y
 
 
+def _bn_mean_rstd(x, training, pre_sums, running_mean, running_var, momentum, eps):
+    """(mean, rstd) fp32 [C] of a BatchNorm over the rows of x.  Training: batch statistics -- from pre_sums, fp32 [2, C] (sum, sum of
+    squares) per channel, where x's producer already summed them, else from a pass over x -- and the running buffers are updated in
+    place; evaluation: the running buffers as they stand."""
+    if training and pre_sums is not None:
+        return hip.bn_stats_from_sums(pre_sums, x.shape[0], running_mean, running_var, momentum, eps)
+    if training:
+        return hip.bn_stats(x, running_mean, running_var, momentum, eps)
+    return running_mean.detach().clone(), torch.rsqrt(running_var.detach() + eps)
+
+
 @direct_grads(1, 2)
 class BatchNormActFn(Function):
     """BatchNorm2d (+ReLU/ReLU6) (+Dropout2d channel scale) on NHWC rows.
@@ -1379,13 +1360,7 @@ class BatchNormActFn(Function):
                 pre_sums=None):
         x = x if x.is_contiguous() else x.contiguous()
         g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        if training and pre_sums is not None:
-            mean, rstd = hip.bn_stats_from_sums(pre_sums, x.shape[0], running_mean, running_var, momentum, eps)
-        elif training:
-            mean, rstd = hip.bn_stats(x, running_mean, running_var, momentum, eps)
-        else:
-            mean = running_mean.detach().clone()
-            rstd = torch.rsqrt(running_var.detach() + eps)
+        mean, rstd = _bn_mean_rstd(x, training, pre_sums, running_mean, running_var, momentum, eps)
         y = hip.bn_apply(x, mean, rstd, g, b, act, chan_scale, rows_per_sample or 1)
         ctx.save_for_backward(x, mean, rstd, g, b, chan_scale)
         ctx.meta = (act, rows_per_sample or 1, not training)
@@ -1422,13 +1397,7 @@ class BnActLinearFn(Function):
         M, K = x.shape
         N = weight.shape[0]
         g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        if training and pre_sums is not None:       # the producer already summed x and x^2 per channel
-            mean, rstd = hip.bn_stats_from_sums(pre_sums, M, running_mean, running_var, momentum, eps)
-        elif training:
-            mean, rstd = hip.bn_stats(x, running_mean, running_var, momentum, eps)
-        else:
-            mean = running_mean.detach().clone()
-            rstd = torch.rsqrt(running_var.detach() + eps)
+        mean, rstd = _bn_mean_rstd(x, training, pre_sums, running_mean, running_var, momentum, eps)
         scale, shift = hip.bn_affine_table(mean, rstd, g, b, chan_scale, M // rps, K)
         w, bp = _padded_rows(weight, bias, N, Np, K, x.dtype, x.device)
         y = hip.gemm_pro(0, x, w, M, Np, K, scale, shift, rps, act, bias=bp)[:, :N]
@@ -1733,13 +1702,7 @@ class Conv3x3Fn(Function):
     def forward(ctx, x, weight, B, H, W, fp8=False):
         x = _rowmajor(x)
         O, I = weight.shape[0], weight.shape[1]
-        wsrc = weight.detach().contiguous()
-        cdt = x.dtype
-
-        def make_wm():
-            t = torch.empty((O, 9, I), dtype=cdt, device=x.device)
-            return t, [('perm', wsrc, t, O, I, 9, I)]
-        wm = derived_weight(wsrc, ('conv3x3', cdt), make_wm).view(O, 9 * I)                         # [O][(ky,kx)][ci]
+        wm = _tap_major(weight, x.dtype, ('conv3x3', x.dtype), x.device)
         use8 = bool(fp8) and x.dtype == torch.bfloat16 and hip.conv3x3_fp8_supported(0, B, H, W, I, O)
         xq = sx = None
         if use8:
@@ -1765,7 +1728,7 @@ class Conv3x3Fn(Function):
         if fp8 and dy.dtype == torch.bfloat16 and (xq is not None or (ctx.needs_input_grad[0] and hip.conv3x3_fp8_supported(1, B, H, W, I, O))):
             gq, sg = hip.quant_tensor_fp8(dy, e5m2=True)          # the gradient in e5m2, one dynamic scale: data and weight gradient share it
         if ctx.needs_input_grad[0]:
-            wt = hip.permute021(w.reshape(1, O, I * 9), 1, O, I * 9, dy.dtype).view(I, 9 * O)             # [ci][(ky,kx)][co]
+            wt = _tap_major_transposed(w, dy.dtype)
             if gq is not None and hip.conv3x3_fp8_supported(1, B, H, W, I, O):
                 wq, sw = hip.quant_rows_fp8(wt)                   # transposed weights e4m3 per input channel
                 dx = hip.conv3x3_fp8(1, gq, sg, wq, sw, B, H, W, I, O)
@@ -1776,7 +1739,7 @@ class Conv3x3Fn(Function):
                 dwm = hip.conv3x3_fp8_wgrad(xq, sx, gq, sg, B, H, W, I, O)
             else:
                 dwm = hip.conv3x3(2, x, dy, B, H, W, I, O, split_k=hip.pick_splitk_conv3x3(I, O, B * H * W))           # [O][(ky,kx)][ci] fp32
-            dw = hip.permute021(dwm.view(O, 9, I), O, 9, I, torch.float32).view(wshape)
+            dw = _from_tap_major(dwm, O, 9, I).view(wshape)
         return dx, dw, None, None, None, None
 
 
@@ -1797,13 +1760,7 @@ class DilatedConv3x3Fn(Function):
     def forward(ctx, x, weight, B, H, W, dilation):
         x = _rowmajor(x)
         O, I = weight.shape[0], weight.shape[1]
-        wsrc = weight.detach().contiguous()
-        cdt = x.dtype
-
-        def make_wm():
-            t = torch.empty((O, 9, I), dtype=cdt, device=x.device)
-            return t, [('perm', wsrc, t, O, I, 9, I)]
-        wm = derived_weight(wsrc, ('conv3x3', cdt), make_wm).view(O, 9 * I)                         # [O][(ky,kx)][ci]
+        wm = _tap_major(weight, x.dtype, ('conv3x3', x.dtype), x.device)
         y = hip.conv3x3_dil(0, x, wm, B, H, W, I, O, dilation)
         ctx.save_for_backward(x, weight.detach())
         ctx.meta = (B, H, W, I, O, weight.shape, dilation)
@@ -1816,11 +1773,11 @@ class DilatedConv3x3Fn(Function):
         dy = _rowmajor(dy)
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            wt = hip.permute021(w.reshape(1, O, I * 9), 1, O, I * 9, dy.dtype).view(I, 9 * O)             # [ci][(ky,kx)][co]
+            wt = _tap_major_transposed(w, dy.dtype)
             dx = hip.conv3x3_dil(1, dy, wt, B, H, W, I, O, dilation)
         if ctx.needs_input_grad[1]:
             dwm = hip.conv3x3_dil(2, x, dy, B, H, W, I, O, dilation)                                        # [O][(ky,kx)][ci] fp32
-            dw = hip.permute021(dwm.view(O, 9, I), O, 9, I, torch.float32).view(wshape)
+            dw = _from_tap_major(dwm, O, 9, I).view(wshape)
         return dx, dw, None, None, None, None
 
 
