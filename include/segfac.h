@@ -679,6 +679,42 @@ int segf_argmax_confmat(int dt, int B, int C, int h, int w, int H, int W, const 
                         const int64_t* target, int64_t ignore_label, int64_t* mat, int64_t* hist,
                         int32_t* flag, int64_t* pred_out /*nullable [B][H][W]*/, void* stream);
 
+/* ---- multi-scale + flip (MSF) evaluation: resample + softmax + sum over n low-resolution maps, arg max of the sum and both
+ * confusion matrices in one kernel (csrc/eval_msf.hip).  The published mIoU protocol: the model runs on the image at several
+ * scales, each also horizontally mirrored; every output is resized to the label size (H, W), softmaxed over the classes, the
+ * probability maps are summed and the arg max of the sum is scored.  No full-resolution map exists here.
+ * Map k: NHWC [B][h_k][w_k][ldl_k >= C] of dtype dt (all maps one dtype), device pointer logits[k]; hw[2k], hw[2k+1] = h_k, w_k;
+ * flip[k] != 0: the map is the model's output for the MIRRORED image.  logits / hw / ldl / flip are HOST arrays of n entries, n <=
+ * SEGF_MSF_MAX_MAPS: the library copies them into a by-value kernel argument of SEGF_MSF_MAX_MAPS entries -- no device table, no
+ * upload, no host synchronisation (the call can be captured into a hipGraph; the host arrays may be freed on return).
+ * For every output pixel (b, Y, X):
+ *   resample   z_k[c] = bilinear sample of map k at (Y, X): source rows / columns / lambdas of F.interpolate(mode='bilinear',
+ *              align_corners=False) at ANY ratio (h_k > H too: downsampling without antialiasing, as F.interpolate does), four taps
+ *              combined in ATen's operation order -- the arithmetic of segf_argmax_confmat's generic path.  h_k == H and w_k == W: the
+ *              row is read directly.  Flip rule: for flip[k] != 0 the tap columns x0, x1 are read at w_k-1-x0, w_k-1-x1 with the same
+ *              weights (exactly the sample of the un-mirrored map; no mirrored copy is made).
+ *   softmax    p_k = softmax_c(z_k), fp32, max-subtracted.
+ *   sum        S[c] = p_0[c] + p_1[c] + ... + p_(n-1)[c], added in map order (summation order = the order of the arrays): two runs
+ *              give the same bits; a permutation of the maps may change the last bits.
+ *   arg max    pred = the lowest class index attaining max_c S[c] (0 on an all-NaN row).
+ *   count      as segf_argmax_confmat: mat += 1 at [t][pred] where 0 <= t < C; hist the same except t == ignore_label; a label outside
+ *              [0, C) that is not ignore_label sets flag[0] bit 0 and is counted nowhere.  target == NULL: no counting (inference).
+ * pred_out (nullable): int64 [B][H][W].  prob_out (nullable): fp32 [B*H*W][ldp >= C], the sums S (NOT divided by n).
+ * SEGF_ERR_SHAPE before any launch: n < 1 or n > SEGF_MSF_MAX_MAPS, C < 1 or C > 192, B < 1 or B > 65535, any h_k, w_k, H, W < 1,
+ * ldl_k < C, prob_out given with ldp < C.  segf_msf_supported: 1 when the shape part of that (and dt) is acceptable, else 0.
+ * Cost: reads every tap row it needs (4 per map and pixel, served from cache: a low-resolution row feeds many pixels), the labels
+ * once, and writes the counts; measured figures in profiles/msf_eval.md.  No floating-point atomics.                      */
+#define SEGF_MSF_MAX_MAPS 16
+int segf_msf_supported(int dt, int B, int C, int n, const int* hw /*HOST [n][2]*/, int H, int W);
+int segf_msf_argmax_confmat(int dt, int B, int C, int n,
+                            void** logits       /*HOST array of n device pointers*/,
+                            const int* hw       /*HOST [n][2] = h_k, w_k*/,
+                            const int64_t* ldl  /*HOST [n]*/,
+                            const int* flip     /*HOST [n]*/,
+                            int H, int W, const int64_t* target, int64_t ignore_label,
+                            int64_t* mat, int64_t* hist, int32_t* flag,
+                            int64_t* pred_out /*nullable*/, float* prob_out /*nullable*/, int64_t ldp, void* stream);
+
 /* out[r] = argmax_c x[r][c] (lowest index on ties): the prediction step of single-image inference
  * (estimate_model.py:104-106, softmax(dim=1).argmax(dim=1) -- softmax is monotonic).  x: [rows][ld >= C], C <= 192. */
 int segf_argmax_rows(int dt, int64_t rows, int C, const void* x, int64_t ld, int64_t* out, void* stream);

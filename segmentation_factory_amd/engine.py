@@ -241,11 +241,105 @@ def train_one_epoch(model, optimizer, dataloader, epoch, device, print_freq, cli
 EVAL_DTYPES = {'fp32': torch.float32, 'bf16': torch.bfloat16}
 
 
+MSF_SCALES = (0.5, 0.75, 1.0, 1.25, 1.5, 1.75)
+
+
+def msf_sizes(H, W, scales, multiple=32):
+    """Network input size per scale of a multi-scale evaluation: the scaled size, each side rounded UP to a multiple of the model
+    stride -- (ceil(int(s H) / multiple) multiple, ceil(int(s W) / multiple) multiple), as semseg's evaluate_msf does."""
+    return [(int(math.ceil(int(s * H) / multiple)) * multiple, int(math.ceil(int(s * W) / multiple)) * multiple) for s in scales]
+
+
+@torch.inference_mode()
+def evaluate_msf(args, model, dataloader, device, print_freq, writer=None, scales=MSF_SCALES, flip=True):
+    """Multi-scale + flip evaluation (the protocol behind the published mIoU figures; semseg's evaluate_msf): every batch runs
+    through the model at each of `scales` (sizes: msf_sizes), with `flip` also horizontally mirrored; the class probabilities of all
+    those outputs, resized to the label size, are summed and the arg max of the sum is scored.  Returns (confmat, metric) like
+    `evaluate`, with the same eval-dtype switch, buffer broadcast and reductions.  The resize of the 3-channel input is a torch op (tiny
+    next to the forward); everything after the forwards is ONE kernel per batch (Metrics.update_msf): no full-resolution logits or
+    probability map exists.
+
+    Aliasing: a GraphedEvalSession replays one graph per input shape and hands back that graph's STATIC output buffer.  The straight
+    and the mirrored forward of one scale share a shape, so the second replay would overwrite the first result before update_msf
+    reads it: the straight result is copied into a buffer kept per shape for the whole evaluation (no allocation per step)."""
+    model.eval()
+    metric = Metrics(args.nb_classes, args.ignore_label, device)
+    confmat = utils.ConfusionMatrix(args.nb_classes)
+    metric_logger = utils.MetricLogger(delimiter="  ")
+    core = model.module if hasattr(model, 'module') else model
+    fused = hasattr(core, 'forward_lowres')
+    eval_dtype = EVAL_DTYPES[str(getattr(args, 'eval_dtype', None) or 'fp32')]
+    trained_dtype = getattr(core, 'compute_dtype', None)
+    switch = hasattr(core, 'set_compute_dtype') and trained_dtype is not None and trained_dtype != eval_dtype
+    if switch:
+        core.set_compute_dtype(eval_dtype)
+    try:
+        return _evaluate_msf(args, model, core, fused, dataloader, device, print_freq, writer, metric, confmat, metric_logger,
+                             tuple(scales), bool(flip))
+    finally:
+        if switch:
+            core.set_compute_dtype(trained_dtype)
+
+
+def _evaluate_msf(args, model, core, fused, dataloader, device, print_freq, writer, metric, confmat, metric_logger, scales, flip):
+    if not scales or len(scales) * (2 if flip else 1) > hip.MSF_MAX_MAPS:
+        raise ValueError(f'evaluate_msf: 1 .. {hip.MSF_MAX_MAPS} maps per image ({len(scales)} scales, flip={flip})')
+    if utils.get_world_size() > 1:
+        from .graph import broadcast_buffers_
+        broadcast_buffers_(core)                                  # as _evaluate: the forwards below bypass the DDP wrapper
+    session = None
+    graph_pref = getattr(args, 'hip_graph', None)
+    if (graph_pref is None or bool(graph_pref)) and fused and torch.device(device).type == 'cuda':
+        from .graph import GraphedEvalSession
+        # one graph per scale (straight and mirrored share it); room for every scale of this call
+        session = GraphedEvalSession(core, max_graphs=max(8, len(scales)), max_captures=max(8, len(scales)))
+    kept = {}                                                     # (shape, dtype) -> copy of the straight result (see the docstring)
+
+    def forward(x):
+        if fused:
+            return session(x) if (session is not None and x.is_cuda) else core.forward_lowres(x)
+        out = model(x)
+        return tokens_from_nchw(out, out.dtype if out.dtype in (torch.float32, torch.bfloat16) else torch.float32)
+
+    for idx, (images, labels) in enumerate(metric_logger.log_every(dataloader, print_freq, 'Test (MSF):')):
+        images = images.to(device, non_blocking=True)
+        labels = labels.to(device, non_blocking=True)
+        H, W = images.shape[2:]
+        maps, flips = [], []
+        for size in msf_sizes(H, W, scales):
+            x = images if size == (H, W) else torch.nn.functional.interpolate(images, size=size, mode='bilinear', align_corners=False)
+            lo = forward(x)
+            if flip and session is not None and x.is_cuda:
+                key = (tuple(lo.data.shape), lo.data.dtype)
+                buf = kept.get(key)
+                if buf is None:
+                    buf = kept[key] = torch.empty_like(lo.data)
+                buf.copy_(lo.data)
+                lo = TokenMap(buf, lo.B, lo.H, lo.W)
+            maps.append(lo)
+            flips.append(0)
+            if flip:
+                maps.append(forward(x.flip(3)))
+                flips.append(1)
+        metric.update_msf(maps, flips, labels, (H, W), confmat=confmat)      # one pass: every map, both matrices
+        if writer and idx % print_freq == 0:
+            writer.add_scalar('valid_mf1', metric.compute_f1()[1])
+            writer.add_scalar('valid_acc', metric.compute_pixel_acc()[1])
+            writer.add_scalar('valid_mIOU', metric.compute_iou()[1])
+    confmat.reduce_from_all_processes()
+    metric.reduce_from_all_processes()
+    return confmat, metric
+
+
 @torch.inference_mode()
 def evaluate(args, model, dataloader, device, print_freq, writer=None):
     """engine.py:74-104.  The reference evaluates in fp32 with autocast deliberately off (engine.py:86-88), whatever precision it
     trained in -- so does this: the forward runs the exact-fp32 kernels unless `args.eval_dtype == 'bf16'` (train_gpu.py
-    --eval-dtype bf16: the production storage type, ~5x the rate; tests/test_model_gpu.py measures what it flips)."""
+    --eval-dtype bf16: the production storage type, ~5x the rate; tests/test_model_gpu.py measures what it flips).
+    `args.eval_scales` (non-empty) or `args.eval_flip` hand the call to evaluate_msf; without them nothing here changes."""
+    if getattr(args, 'eval_scales', None) or getattr(args, 'eval_flip', False):
+        return evaluate_msf(args, model, dataloader, device, print_freq, writer,
+                            scales=tuple(getattr(args, 'eval_scales', None) or (1.0,)), flip=bool(getattr(args, 'eval_flip', False)))
     model.eval()
     metric = Metrics(args.nb_classes, args.ignore_label, device)
     confmat = utils.ConfusionMatrix(args.nb_classes)

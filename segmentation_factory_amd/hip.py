@@ -1665,6 +1665,43 @@ def argmax_confmat(logits, B, Cc, h, w, H, W, target, ignore_label, mat, hist, f
          'segf_argmax_confmat')
 
 
+MSF_MAX_MAPS = 16          # SEGF_MSF_MAX_MAPS of include/segfac.h
+
+
+def msf_argmax_confmat(maps, flips, B, Cc, H, W, target, ignore_label, mat, hist, flag, pred_out=None, prob_out=None):
+    """segf_msf_argmax_confmat: multi-scale + flip evaluation in one kernel.  maps: TokenMaps (or (rows, h, w) tuples; rows =
+    [B*h*w, >= Cc] with unit inner stride, all one dtype); flips: one flag per map (the map belongs to the mirrored image).  Per pixel of
+    the (H, W) output: bilinear sample of every map, softmax, sum in list order, arg max -> mat / hist / flag as argmax_confmat
+    (target None: no counting), pred_out int64 [B, H, W], prob_out fp32 [B*H*W, >= Cc] = the summed probabilities.  The descriptors go
+    by value through host arrays: nothing is uploaded, so the call can be captured."""
+    n = len(maps)
+    if len(flips) != n:
+        raise ValueError(f'msf_argmax_confmat: {n} maps but {len(flips)} flip flags')
+    rows, hw = [], []
+    for m in maps:
+        data, h, w = (m.data, m.H, m.W) if hasattr(m, 'data') else m
+        _need_cuda(data)
+        if (data.dtype != (rows[0].dtype if rows else data.dtype) or data.ndim != 2 or data.stride(1) != 1 or data.shape[0] != B * h * w
+                or data.shape[1] < Cc):
+            raise ValueError('msf_argmax_confmat: maps must share one dtype and be [B*h*w, >=C] rows with unit inner stride')
+        rows.append(data)
+        hw += [int(h), int(w)]
+    _need_cuda(target, mat, hist, flag, pred_out, prob_out)
+    if target is not None:
+        assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == B * H * W
+        assert all(t.dtype == torch.int64 and t.is_contiguous() and t.numel() == Cc * Cc for t in (mat, hist)) and flag.dtype == torch.int32
+    assert pred_out is None or (pred_out.dtype == torch.int64 and pred_out.is_contiguous() and pred_out.numel() == B * H * W)
+    assert prob_out is None or (prob_out.dtype == torch.float32 and prob_out.ndim == 2 and prob_out.stride(1) == 1
+                                and prob_out.shape[0] == B * H * W and prob_out.shape[1] >= Cc)
+    ptrs = (C.c_void_p * max(n, 1))(*[r.data_ptr() for r in rows])
+    c_hw = (C.c_int * max(2 * n, 1))(*hw)
+    c_ld = (C.c_int64 * max(n, 1))(*[r.stride(0) for r in rows])
+    c_fl = (C.c_int * max(n, 1))(*[1 if f else 0 for f in flips])
+    _chk(lib().segf_msf_argmax_confmat(dt_of(rows[0]) if rows else F32, B, Cc, n, ptrs, c_hw, c_ld, c_fl, H, W, _ptr(target),
+                                       int(ignore_label), _ptr(mat), _ptr(hist), _ptr(flag), _ptr(pred_out), _ptr(prob_out),
+                                       prob_out.stride(0) if prob_out is not None else 0, _stream()), 'segf_msf_argmax_confmat')
+
+
 def confmat_pairs(gt, pred, Cc, ignore_label, mat, hist, flag):
     _need_cuda(gt, pred)
     _chk(lib().segf_confmat_pairs(_ptr(gt), _ptr(pred), gt.numel(), Cc, int(ignore_label), _ptr(mat), _ptr(hist),

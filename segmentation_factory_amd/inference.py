@@ -82,8 +82,45 @@ class SemSeg:
                 img = orig_img.to(img.device).permute(1, 2, 0) * 0.4 + img * 0.6
         return seg.squeeze(0), img
 
-    def predict(self, image: torch.Tensor, overlay: bool = True):
-        """image: uint8 CHW tensor (what torchvision.io.read_image returns).  -> (seg_map, colour image or None)."""
+    @torch.inference_mode()
+    def msf_maps(self, x: torch.Tensor, scales, flip: bool):
+        """Head outputs of the preprocessed image x at every scale (engine.msf_sizes of x's size), each also for the mirrored
+        input when `flip`: ([TokenMap], [flip flag]) in the order the probabilities are summed."""
+        from .engine import msf_sizes
+        H1, W1 = x.shape[2:]
+        maps, flips = [], []
+        for size in msf_sizes(H1, W1, scales):
+            xs = x if size == (H1, W1) else torch.nn.functional.interpolate(x, size=size, mode='bilinear', align_corners=False)
+            maps.append(self.model_forward(xs))
+            flips.append(0)
+            if flip:
+                maps.append(self.model_forward(xs.flip(3)))
+                flips.append(1)
+        return maps, flips
+
+    @torch.inference_mode()
+    def postprocess_msf(self, orig_hw, maps, flips, orig_img=None, overlay=False):
+        """Multi-scale + flip prediction: every map resampled to the original size (bilinear, align_corners=False), softmaxed and
+        summed, arg max of the sum -- one kernel (hip.msf_argmax_confmat without labels), its pred_out is the segmentation map."""
+        H0, W0 = orig_hw
+        B = maps[0].B
+        nc = self.model.num_classes if hasattr(self.model, 'num_classes') else maps[0].data.shape[1]
+        seg = torch.empty((B, H0, W0), dtype=torch.int64, device=maps[0].data.device)
+        hip.msf_argmax_confmat(maps, flips, B, nc, H0, W0, None, -1, None, None, None, pred_out=seg)
+        img = None
+        if self.palette is not None:
+            img = self.palette[seg].squeeze(0)
+            if overlay and orig_img is not None:
+                img = orig_img.to(img.device).permute(1, 2, 0) * 0.4 + img * 0.6
+        return seg.squeeze(0), img
+
+    def predict(self, image: torch.Tensor, overlay: bool = True, scales=None, flip: bool = False):
+        """image: uint8 CHW tensor (what torchvision.io.read_image returns).  -> (seg_map, colour image or None).
+        scales (e.g. (0.5, 0.75, 1.0, 1.25, 1.5, 1.75)) and / or flip: multi-scale + flip prediction (postprocess_msf); without
+        them the single forward of the reference."""
         x = self.preprocess(image)
+        if scales or flip:
+            maps, flips = self.msf_maps(x, tuple(scales) if scales else (1.0,), bool(flip))
+            return self.postprocess_msf(tuple(image.shape[1:]), maps, flips, image, overlay)
         lo = self.model_forward(x)
         return self.postprocess(tuple(image.shape[1:]), lo, tuple(x.shape[2:]), image, overlay)

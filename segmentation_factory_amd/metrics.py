@@ -2,7 +2,8 @@
 
 ``hist`` stays an fp32 [n, n] tensor accumulated per batch (quirk Q5: exact only below 2**24 per cell), rows =
 ground truth.  Counting happens on device: ``update`` takes materialised NCHW logits like the reference;
-``update_lowres`` takes the head output and fuses upsample + argmax + histogram in one kernel.
+``update_lowres`` takes the head output and fuses upsample + argmax + histogram in one kernel; ``update_msf`` takes the head outputs
+of one batch at several scales / mirrored (multi-scale + flip evaluation) and fuses resample + softmax + sum + argmax + histogram.
 """
 import torch
 import torch.distributed as dist
@@ -36,12 +37,10 @@ class Metrics:
         tm = tokens_from_nchw(pred, pred.dtype if pred.dtype in (torch.float32, torch.bfloat16) else torch.float32)
         self.update_lowres(tm, target, (H, W))
 
-    def update_lowres(self, lowres: TokenMap, target: torch.Tensor, size, confmat=None):
-        """Fused bilinear-upsample + argmax + counting.  Optionally also feeds a utils.ConfusionMatrix (valid iff
-        0 <= t < n) from the same pass, as engine.evaluate needs both (engine.py:90-91)."""
-        H, W = size
+    def _count_targets(self, dev, target, confmat):
+        """(counts, flag, mat, int64 contiguous target) of one counting pass: the static scratch and the matrix that takes the
+        ConfusionMatrix half (the caller's, or an unused static one)."""
         n = self.num_classes
-        dev = lowres.data.device
         counts, flag = self._scratch(dev)
         if confmat is not None:
             confmat._ensure(dev)
@@ -52,8 +51,28 @@ class Metrics:
             mat = self._mat_unused
         if target.dtype != torch.int64 or not target.is_contiguous():
             target = target.contiguous().to(torch.int64)
+        return counts, flag, mat, target
+
+    def update_lowres(self, lowres: TokenMap, target: torch.Tensor, size, confmat=None):
+        """Fused bilinear-upsample + argmax + counting.  Optionally also feeds a utils.ConfusionMatrix (valid iff
+        0 <= t < n) from the same pass, as engine.evaluate needs both (engine.py:90-91)."""
+        H, W = size
+        n = self.num_classes
+        counts, flag, mat, target = self._count_targets(lowres.data.device, target, confmat)
         hip.argmax_confmat(lowres.data, lowres.B, n, lowres.H, lowres.W, H, W, target, self.ignore_label, mat, counts, flag)
         hip.hist_accum_(self.hist, counts)        # hist (fp32) += this batch's int64 counts, as the reference's `self.hist += bincount`
+
+    def update_msf(self, lowres_list, flips, target: torch.Tensor, size, confmat=None):
+        """Multi-scale + flip counting: `lowres_list` holds the head outputs (TokenMaps) of one batch at every scale, `flips[k]` says
+        that map k belongs to the horizontally mirrored image.  One kernel resamples every map to `size`, softmaxes, sums the
+        probabilities in list order, takes the arg max and counts -- the same static scratch, the same hist_accum_ and the same
+        one-pass feeding of both matrices as update_lowres; no full-resolution map exists."""
+        H, W = size
+        n = self.num_classes
+        first = lowres_list[0]
+        counts, flag, mat, target = self._count_targets(first.data.device, target, confmat)
+        hip.msf_argmax_confmat(lowres_list, flips, first.B, n, H, W, target, self.ignore_label, mat, counts, flag)
+        hip.hist_accum_(self.hist, counts)
 
     def _finish(self, v):
         m = v[~v.isnan()].mean().item()

@@ -127,6 +127,11 @@ def get_args_parser():
     parser.add_argument('--eval-dtype', default='fp32', choices=['fp32', 'bf16'],
                         help="precision of evaluate()'s forward: fp32 as the reference (engine.py:86-88 switches autocast off), or the "
                              'bf16 production storage type')
+    parser.add_argument('--eval-scales', dest='eval_scales', nargs='+', type=float, default=None,
+                        help='multi-scale evaluation (--eval and the per-epoch validation): run the model at these scales of the input '
+                             '(e.g. 0.5 0.75 1.0 1.25 1.5 1.75), sum the class probabilities, score the arg max of the sum')
+    parser.add_argument('--eval-flip', dest='eval_flip', action='store_true', default=False,
+                        help='evaluation also runs every scale on the horizontally mirrored image (with --eval-scales: the MSF protocol)')
     parser.add_argument('--loss', default='ce_dice', choices=['ce_dice', 'CrossEntropy', 'OhemCrossEntropy', 'FocalLoss'],
                         help="training loss: ce_dice = the reference engine's criterion (CE + Dice, see --dice), or one of the classes of "
                              'util/losses.py on the fused low-resolution loss path (segmentation_factory_amd/losses.py; --dice is not consulted)')
