@@ -715,6 +715,41 @@ int segf_msf_argmax_confmat(int dt, int B, int C, int n,
                             int64_t* mat, int64_t* hist, int32_t* flag,
                             int64_t* pred_out /*nullable*/, float* prob_out /*nullable*/, int64_t ldp, void* stream);
 
+/* ---- sliding-window evaluation: resample + mean over the low-resolution maps of overlapping crops, arg max of the mean and both
+ * confusion matrices in one kernel (csrc/eval_slide.hip).  The other published protocol (mmseg's slide_inference): the model runs on
+ * overlapping ch x cw crops of the image, every crop's logits are resized to the crop, the logits of overlapping crops are averaged
+ * and the arg max of the mean is scored.  No full-resolution map, accumulator or count map exists here.
+ * Grid: ny = max(H - ch + sh - 1, 0) / sh + 1 windows down and nx = max(W - cw + sw - 1, 0) / sw + 1 across (integer division);
+ * window (i, j) has origin y_i = min(i sh, H - ch), x_j = min(j sw, W - cw): the last window of an axis is shifted back so that it
+ * ends at the border, two windows never coincide, and every window has size exactly ch x cw.  segf_slide_grid writes ny, nx.
+ * logits: ONE device buffer [B][ny nx][h][w][ldl >= C] of dtype dt, window index i nx + j: the head outputs of the windows, (h, w)
+ * being the head's output size for a ch x cw input.  64-bit indexing throughout.
+ * For every output pixel (b, Y, X), over every window that covers it (y_i <= Y < y_i + ch, x_j <= X < x_j + cw), in ascending
+ * (i, j) order (i outer, j inner):
+ *   resample   z_ij[c] = bilinear sample of the window's map at the local pixel (Y - y_i, X - x_j): source rows / columns / lambdas
+ *              of F.interpolate(size=(ch, cw), mode='bilinear', align_corners=False) at ANY ratio (h > ch too), four taps combined in
+ *              ATen's operation order -- the arithmetic of segf_argmax_confmat's generic path.  h == ch and w == cw: the row is read
+ *              directly.
+ *   sum        A[c] = z_ij[c] + ..., fp32, added in window order: the same sequence of additions on every run (same bits).
+ *   mean       M[c] = A[c] / n, n = the number of covering windows: a true IEEE fp32 division, not a reciprocal approximation -- a
+ *              pixel covered once keeps its sample bit for bit.
+ *   arg max    pred = the lowest class index attaining max_c M[c] (0 on an all-NaN row).
+ *   count      as segf_argmax_confmat: mat += 1 at [t][pred] where 0 <= t < C; hist the same except t == ignore_label; a label outside
+ *              [0, C) that is not ignore_label sets flag[0] bit 0 and is counted nowhere.  target == NULL: no counting (inference).
+ * pred_out (nullable): int64 [B][H][W].  mean_out (nullable): fp32 [B*H*W][ldm >= C], the mean logits M.
+ * SEGF_ERR_SHAPE before any launch: C < 1 or C > 192, B < 1 or B > 65535, any of H, W, h, w < 1, 1 <= sh <= ch <= H or
+ * 1 <= sw <= cw <= W violated (a stride larger than the crop would leave pixels uncovered), ldl < C, mean_out given with ldm < C,
+ * logits NULL; SEGF_ERR_DTYPE for an unknown dt.  segf_slide_supported: 1 when the shape part of that (without the row strides and
+ * pointers) and dt are acceptable, else 0.  segf_slide_grid: 0, or SEGF_ERR_SHAPE for a grid refused above (or NULL ny / nx).
+ * No device table, no upload, no host synchronisation (the call can be captured into a hipGraph); no floating-point atomics: two runs
+ * give the same bits.  Measured figures in profiles/slide_eval.md.                                                       */
+int segf_slide_grid(int H, int W, int ch, int cw, int sh, int sw, int* ny, int* nx);
+int segf_slide_supported(int dt, int B, int C, int H, int W, int ch, int cw, int sh, int sw, int h, int w);
+int segf_slide_argmax_confmat(int dt, int B, int C, int H, int W, int ch, int cw, int sh, int sw, int h, int w,
+                              const void* logits, int64_t ldl, const int64_t* target, int64_t ignore_label,
+                              int64_t* mat, int64_t* hist, int32_t* flag,
+                              int64_t* pred_out /*nullable*/, float* mean_out /*nullable*/, int64_t ldm, void* stream);
+
 /* out[r] = argmax_c x[r][c] (lowest index on ties): the prediction step of single-image inference
  * (estimate_model.py:104-106, softmax(dim=1).argmax(dim=1) -- softmax is monotonic).  x: [rows][ld >= C], C <= 192. */
 int segf_argmax_rows(int dt, int64_t rows, int C, const void* x, int64_t ld, int64_t* out, void* stream);

@@ -13,16 +13,12 @@
 // or workgroups except the fixed-shape butterfly of the softmax denominator -- two runs give the same bits.  Counts are integer
 // atomics (confmat_count of loss.hip).  The per-map descriptors travel BY VALUE in the kernel argument (MsfMaps, 512 bytes): no
 // device table, no upload, no host synchronisation, so the call can be captured into a hipGraph.
-#include "common.h"
+#include "eval_rows.h"
 
 struct MsfMap { const void* p; int64_t ldl; int h, w, flip, pad; };
 struct MsfMaps { MsfMap m[SEGF_MSF_MAX_MAPS]; };
 
 #define MSF_THREADS 256
-
-// reductions over the GW lanes of a pixel's group (every lane of the wave active); GW == 64: wave-uniform result
-template <int GW> __device__ __forceinline__ float grp_max(float v) { return GW == 64 ? wave_max_all(v) : wave_max(v, GW); }
-template <int GW> __device__ __forceinline__ float grp_sum(float v) { return GW == 64 ? wave_sum_all(v) : wave_sum(v, GW); }
 
 template <typename T, int NS, int GW>
 __global__ void __launch_bounds__(MSF_THREADS) msf_argmax_confmat_kernel(MsfMaps maps, int n, int C, int H, int W,
@@ -100,19 +96,7 @@ __global__ void __launch_bounds__(MSF_THREADS) msf_argmax_confmat_kernel(MsfMaps
 #pragma unroll
             for (int s = 0; s < NS; ++s) S[s] += e[s] * inv;
         }
-        // arg max of the sums: lowest class index attaining the maximum (wave_argmax of loss.hip, per group); 0 on an all-NaN row
-        float zs[NS];
-#pragma unroll
-        for (int s = 0; s < NS; ++s) zs[s] = cl + 64 * s < C ? S[s] : -INFINITY;
-        float mx = zs[0];
-#pragma unroll
-        for (int s = 1; s < NS; ++s) mx = fmaxf(mx, zs[s]);
-        mx = grp_max<GW>(mx);
-        float cand = -1e9f;                                       // -(index): the lowest index is the maximum of the negated ones
-#pragma unroll
-        for (int s = NS - 1; s >= 0; --s) if (zs[s] == mx) cand = -(float)(cl + 64 * s);
-        const int bi = (int)(-grp_max<GW>(cand));
-        const int best = bi < C ? bi : 0;
+        const int best = grp_argmax<NS, GW>(S, cl, C);           // lowest class index attaining the maximum; 0 on an all-NaN row
         if (need) {
             const int64_t q = (int64_t)b * npix + p;
             if (prob_out) {
@@ -122,13 +106,7 @@ __global__ void __launch_bounds__(MSF_THREADS) msf_argmax_confmat_kernel(MsfMaps
             }
             if (cl == 0) {
                 if (pred_out) pred_out[q] = best;
-                if (tg) {                                         // confmat_count of loss.hip
-                    if (in_mat) atomicAdd(mat + t * C + best, 1ull);
-                    if (t != ignore_label) {
-                        if (in_mat) atomicAdd(hist + t * C + best, 1ull);
-                        else atomicOr(flag, 1);                   // label outside [0, C) that is not ignore_label
-                    }
-                }
+                if (tg) eval_count(t, best, C, ignore_label, mat, hist, flag);
             }
         }
     }

@@ -331,12 +331,132 @@ def _evaluate_msf(args, model, core, fused, dataloader, device, print_freq, writ
     return confmat, metric
 
 
+def slide_windows(H, W, crop, stride):
+    """Window grid of a sliding-window evaluation over an H x W image (mmseg's slide_inference; segf_slide_grid of include/segfac.h):
+    -> (crop_eff, stride_eff, [(y, x), ...]) in window order (rows of windows, then columns).  The crop is clamped to the image,
+    crop_eff = (min(ch, H), min(cw, W)), and the stride to the crop, stride_eff = min(stride, crop_eff) per axis; an axis has
+    max(L - crop + stride - 1, 0) // stride + 1 windows, window i at min(i stride, L - crop): the last one is moved back to end at the
+    border."""
+    (ch, cw), (sh, sw) = hip.hw_pair(crop, 'crop'), hip.hw_pair(stride, 'stride')
+    if min(H, W, ch, cw, sh, sw) < 1:
+        raise ValueError(f'slide_windows: sizes must be positive (image {H} x {W}, crop {ch} x {cw}, stride {sh} x {sw})')
+    ch, cw = min(ch, H), min(cw, W)
+    sh, sw = min(sh, ch), min(sw, cw)
+    ys = [min(i * sh, H - ch) for i in range(max(H - ch + sh - 1, 0) // sh + 1)]
+    xs = [min(j * sw, W - cw) for j in range(max(W - cw + sw - 1, 0) // sw + 1)]
+    return (ch, cw), (sh, sw), [(y, x) for y in ys for x in xs]
+
+
+def default_slide_stride(crop):
+    """floor(2 crop / 3) per axis, at least 1: 512 -> 341, 1024 -> 682."""
+    ch, cw = hip.hw_pair(crop, 'crop')
+    return max(2 * ch // 3, 1), max(2 * cw // 3, 1)
+
+
+@torch.inference_mode()
+def evaluate_slide(args, model, dataloader, device, print_freq, writer=None, crop=512, stride=None, window_batch=None):
+    """Sliding-window evaluation (mmseg's slide_inference, the protocol behind SegFormer's Cityscapes figures and most ADE20K / VOC
+    configurations): every image is cut into overlapping `crop` windows at `stride` (slide_windows; stride None: floor(2 crop / 3)), the
+    model runs on the windows, the logits of overlapping windows -- each resized to the crop -- are averaged and the arg max of the mean
+    is scored.  Returns (confmat, metric) like `evaluate`, with the same eval-dtype switch, buffer broadcast and reductions.  The
+    windows are torch slices of the 3-channel input; everything after the forwards is ONE kernel per batch (Metrics.update_slide): no
+    full-resolution logits, accumulator or count map exists.
+
+    window_batch None: all B nWin windows of a batch go through one forward.  An integer: chunks of at most that many; their outputs
+    land in ONE buffer kept per shape for the whole evaluation (no allocation per step).  Aliasing (as in evaluate_msf): chunks share a
+    shape, hence a graph of the GraphedEvalSession, hence its STATIC output buffer -- each chunk is copied out before the next replay."""
+    model.eval()
+    metric = Metrics(args.nb_classes, args.ignore_label, device)
+    confmat = utils.ConfusionMatrix(args.nb_classes)
+    metric_logger = utils.MetricLogger(delimiter="  ")
+    core = model.module if hasattr(model, 'module') else model
+    fused = hasattr(core, 'forward_lowres')
+    eval_dtype = EVAL_DTYPES[str(getattr(args, 'eval_dtype', None) or 'fp32')]
+    trained_dtype = getattr(core, 'compute_dtype', None)
+    switch = hasattr(core, 'set_compute_dtype') and trained_dtype is not None and trained_dtype != eval_dtype
+    if switch:
+        core.set_compute_dtype(eval_dtype)
+    try:
+        return _evaluate_slide(args, model, core, fused, dataloader, device, print_freq, writer, metric, confmat, metric_logger,
+                               hip.hw_pair(crop, 'crop'), hip.hw_pair(stride, 'stride') if stride is not None else default_slide_stride(crop),
+                               window_batch)
+    finally:
+        if switch:
+            core.set_compute_dtype(trained_dtype)
+
+
+def _evaluate_slide(args, model, core, fused, dataloader, device, print_freq, writer, metric, confmat, metric_logger, crop, stride,
+                    window_batch):
+    if window_batch is not None and int(window_batch) < 1:
+        raise ValueError(f'evaluate_slide: window_batch must be at least 1, got {window_batch}')
+    if utils.get_world_size() > 1:
+        from .graph import broadcast_buffers_
+        broadcast_buffers_(core)                                  # as _evaluate: the forwards below bypass the DDP wrapper
+    session = None
+    graph_pref = getattr(args, 'hip_graph', None)
+    if (graph_pref is None or bool(graph_pref)) and fused and torch.device(device).type == 'cuda':
+        from .graph import GraphedEvalSession
+        session = GraphedEvalSession(core)                        # one graph per chunk shape (full chunks and the remainder)
+    kept = {}                                                     # (rows, columns, dtype) -> the windows' buffer (see the docstring)
+
+    def forward(x):
+        if fused:
+            return session(x) if (session is not None and x.is_cuda) else core.forward_lowres(x)
+        out = model(x)
+        return tokens_from_nchw(out, out.dtype if out.dtype in (torch.float32, torch.bfloat16) else torch.float32)
+
+    for idx, (images, labels) in enumerate(metric_logger.log_every(dataloader, print_freq, 'Test (slide):')):
+        images = images.to(device, non_blocking=True)
+        labels = labels.to(device, non_blocking=True)
+        B = images.shape[0]
+        H, W = images.shape[2:]
+        (ch, cw), strd, origins = slide_windows(H, W, crop, stride)
+        n = B * len(origins)
+        # image-major, then window order: the layout segf_slide_argmax_confmat reads
+        x = torch.stack([images[:, :, y:y + ch, x0:x0 + cw] for y, x0 in origins], dim=1).reshape(n, images.shape[1], ch, cw)
+        if window_batch is None or int(window_batch) >= n:
+            lo = forward(x)
+            windows = (lo.data, lo.H, lo.W)
+        else:
+            buf = None
+            for k in range(0, n, int(window_batch)):
+                lo = forward(x[k:k + int(window_batch)])
+                per = lo.H * lo.W                                 # rows per window
+                if buf is None:
+                    key = (n * per, lo.data.shape[1], lo.data.dtype)
+                    buf = kept.get(key)
+                    if buf is None:
+                        buf = kept[key] = torch.empty((n * per, lo.data.shape[1]), dtype=lo.data.dtype, device=lo.data.device)
+                buf[k * per:k * per + lo.data.shape[0]].copy_(lo.data)        # out of the graph's static buffer before the next replay
+            windows = (buf, lo.H, lo.W)
+        metric.update_slide(windows, labels, (H, W), (ch, cw), strd, confmat=confmat)     # one pass: every window, both matrices
+        if writer and idx % print_freq == 0:
+            writer.add_scalar('valid_mf1', metric.compute_f1()[1])
+            writer.add_scalar('valid_acc', metric.compute_pixel_acc()[1])
+            writer.add_scalar('valid_mIOU', metric.compute_iou()[1])
+    confmat.reduce_from_all_processes()
+    metric.reduce_from_all_processes()
+    return confmat, metric
+
+
 @torch.inference_mode()
 def evaluate(args, model, dataloader, device, print_freq, writer=None):
     """engine.py:74-104.  The reference evaluates in fp32 with autocast deliberately off (engine.py:86-88), whatever precision it
     trained in -- so does this: the forward runs the exact-fp32 kernels unless `args.eval_dtype == 'bf16'` (train_gpu.py
     --eval-dtype bf16: the production storage type, ~5x the rate; tests/test_model_gpu.py measures what it flips).
-    `args.eval_scales` (non-empty) or `args.eval_flip` hand the call to evaluate_msf; without them nothing here changes."""
+    `args.eval_scales` (non-empty) or `args.eval_flip` hand the call to evaluate_msf; without them nothing here changes.
+    `args.eval_mode == 'slide'` hands it to evaluate_slide (args.eval_crop, default args.image_size; args.eval_stride, default
+    floor(2 crop / 3); args.eval_window_batch); sliding windows at several scales or mirrored are not built: ValueError."""
+    if getattr(args, 'eval_mode', 'whole') == 'slide':
+        scales = tuple(getattr(args, 'eval_scales', None) or (1.0,))
+        if scales != (1.0,) or getattr(args, 'eval_flip', False):
+            raise ValueError("evaluate: eval_mode 'slide' with eval_scales other than (1.0,) or with eval_flip -- sliding windows at "
+                             'several scales or mirrored are not built')
+        crop = getattr(args, 'eval_crop', None) or getattr(args, 'image_size', None)
+        if crop is None:
+            raise ValueError("evaluate: eval_mode 'slide' needs args.eval_crop (or args.image_size)")
+        return evaluate_slide(args, model, dataloader, device, print_freq, writer, crop=crop, stride=getattr(args, 'eval_stride', None),
+                              window_batch=getattr(args, 'eval_window_batch', None))
     if getattr(args, 'eval_scales', None) or getattr(args, 'eval_flip', False):
         return evaluate_msf(args, model, dataloader, device, print_freq, writer,
                             scales=tuple(getattr(args, 'eval_scales', None) or (1.0,)), flip=bool(getattr(args, 'eval_flip', False)))

@@ -1702,6 +1702,53 @@ def msf_argmax_confmat(maps, flips, B, Cc, H, W, target, ignore_label, mat, hist
                                        prob_out.stride(0) if prob_out is not None else 0, _stream()), 'segf_msf_argmax_confmat')
 
 
+def hw_pair(v, name='size'):
+    """(rows, columns) of an int, a 1-list or a pair: crop / stride of the sliding-window calls."""
+    v = tuple(v) if isinstance(v, (tuple, list)) else (v,)
+    if len(v) not in (1, 2):
+        raise ValueError(f'{name}: expected H or (H, W), got {v!r}')
+    return int(v[0]), int(v[-1])
+
+
+def slide_grid(H, W, crop, stride):
+    """segf_slide_grid: (ny, nx) of the sliding-window grid over an H x W image -- n = max(L - crop + stride - 1, 0) // stride + 1
+    per axis, window i at min(i stride, L - crop).  crop / stride: an int or (rows, columns).  ValueError for a grid the library
+    refuses (1 <= stride <= crop <= image violated)."""
+    (ch, cw), (sh, sw) = hw_pair(crop, 'crop'), hw_pair(stride, 'stride')
+    ny, nx = _i(), _i()
+    if lib().segf_slide_grid(int(H), int(W), ch, cw, sh, sw, C.byref(ny), C.byref(nx)) != 0:
+        raise ValueError(f'slide_grid: 1 <= stride <= crop <= image violated (image {H} x {W}, crop {ch} x {cw}, stride {sh} x {sw})')
+    return ny.value, nx.value
+
+
+def slide_argmax_confmat(windows, B, Cc, H, W, crop, stride, target, ignore_label, mat, hist, flag, pred_out=None, mean_out=None):
+    """segf_slide_argmax_confmat: sliding-window evaluation in one kernel.  windows: a TokenMap (or a (rows, h, w) tuple) holding the
+    head outputs of all windows of the batch, rows = [B*ny*nx*h*w, >= Cc] with unit inner stride, image-major, then window order
+    (i nx + j; slide_grid gives ny, nx).  Per pixel of the (H, W) output: bilinear sample of every covering window's map at the local
+    pixel, summed in window order, divided by the cover count, arg max -> mat / hist / flag as argmax_confmat (target None: no
+    counting), pred_out int64 [B, H, W], mean_out fp32 [B*H*W, >= Cc] = the mean logits.  Nothing is uploaded: the call can be
+    captured."""
+    (ch, cw), (sh, sw) = hw_pair(crop, 'crop'), hw_pair(stride, 'stride')
+    ny, nx = slide_grid(H, W, (ch, cw), (sh, sw))
+    data, h, w = (windows.data, windows.H, windows.W) if hasattr(windows, 'data') else windows
+    h, w = int(h), int(w)
+    _need_cuda(data, target, mat, hist, flag, pred_out, mean_out)
+    if data.ndim != 2 or data.stride(1) != 1 or data.shape[0] != B * ny * nx * h * w or data.shape[1] < Cc:
+        raise ValueError(f'slide_argmax_confmat: windows must be [B*ny*nx*h*w, >=C] rows with unit inner stride '
+                         f'(B {B}, grid {ny} x {nx}, map {h} x {w}, C {Cc}; got {tuple(data.shape)}, strides {tuple(data.stride())})')
+    if hasattr(windows, 'B') and windows.B != B * ny * nx:
+        raise ValueError(f'slide_argmax_confmat: {windows.B} window maps, expected B*ny*nx = {B * ny * nx}')
+    if target is not None:
+        assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == B * H * W
+        assert all(t.dtype == torch.int64 and t.is_contiguous() and t.numel() == Cc * Cc for t in (mat, hist)) and flag.dtype == torch.int32
+    assert pred_out is None or (pred_out.dtype == torch.int64 and pred_out.is_contiguous() and pred_out.numel() == B * H * W)
+    assert mean_out is None or (mean_out.dtype == torch.float32 and mean_out.ndim == 2 and mean_out.stride(1) == 1
+                                and mean_out.shape[0] == B * H * W and mean_out.shape[1] >= Cc)
+    _chk(lib().segf_slide_argmax_confmat(dt_of(data), B, Cc, H, W, ch, cw, sh, sw, h, w, _ptr(data), data.stride(0), _ptr(target),
+                                         int(ignore_label), _ptr(mat), _ptr(hist), _ptr(flag), _ptr(pred_out), _ptr(mean_out),
+                                         mean_out.stride(0) if mean_out is not None else 0, _stream()), 'segf_slide_argmax_confmat')
+
+
 def confmat_pairs(gt, pred, Cc, ignore_label, mat, hist, flag):
     _need_cuda(gt, pred)
     _chk(lib().segf_confmat_pairs(_ptr(gt), _ptr(pred), gt.numel(), Cc, int(ignore_label), _ptr(mat), _ptr(hist),

@@ -60,6 +60,15 @@ class SemSeg:
         """Head output at stride 4 as NHWC token rows (the full-resolution logits tensor is formed in postprocess)."""
         return self.model.forward_lowres(img)
 
+    def _colour(self, seg, orig_img, overlay):
+        """Palette image of a [1, H0, W0] segmentation map (None without a palette), optionally blended over the original image."""
+        if self.palette is None:
+            return None
+        img = self.palette[seg].squeeze(0)
+        if overlay and orig_img is not None:
+            img = orig_img.to(img.device).permute(1, 2, 0) * 0.4 + img * 0.6
+        return img
+
     @torch.inference_mode()
     def postprocess(self, orig_hw, lo: TokenMap, in_hw, orig_img=None, overlay=False):
         """-> (seg_map int64 [H0, W0], colour image uint8/float [H0, W0, 3] or None)."""
@@ -75,12 +84,7 @@ class SemSeg:
         full = torch.empty((B * H0 * W0, ld), dtype=torch.float32, device=low.device)
         hip.bilinear_fwd(mid, B, H1, W1, ld, H0, W0, full, align_corners=True)      # estimate_model.py:102
         seg = hip.argmax_rows(full, nc).view(B, H0, W0)                             # :104
-        img = None
-        if self.palette is not None:
-            img = self.palette[seg].squeeze(0)
-            if overlay and orig_img is not None:
-                img = orig_img.to(img.device).permute(1, 2, 0) * 0.4 + img * 0.6
-        return seg.squeeze(0), img
+        return seg.squeeze(0), self._colour(seg, orig_img, overlay)
 
     @torch.inference_mode()
     def msf_maps(self, x: torch.Tensor, scales, flip: bool):
@@ -107,18 +111,41 @@ class SemSeg:
         nc = self.model.num_classes if hasattr(self.model, 'num_classes') else maps[0].data.shape[1]
         seg = torch.empty((B, H0, W0), dtype=torch.int64, device=maps[0].data.device)
         hip.msf_argmax_confmat(maps, flips, B, nc, H0, W0, None, -1, None, None, None, pred_out=seg)
-        img = None
-        if self.palette is not None:
-            img = self.palette[seg].squeeze(0)
-            if overlay and orig_img is not None:
-                img = orig_img.to(img.device).permute(1, 2, 0) * 0.4 + img * 0.6
-        return seg.squeeze(0), img
+        return seg.squeeze(0), self._colour(seg, orig_img, overlay)
 
-    def predict(self, image: torch.Tensor, overlay: bool = True, scales=None, flip: bool = False):
+    @torch.inference_mode()
+    def predict_slide(self, x: torch.Tensor, orig_hw, crop, stride, orig_img=None, overlay=False):
+        """Sliding-window prediction of the preprocessed image x: the model runs on the overlapping windows of engine.slide_windows
+        (crop clamped to x), the windows' logits are averaged and the arg max of the mean is taken -- one kernel
+        (hip.slide_argmax_confmat without labels), its pred_out is the segmentation map at x's size; an original size that differs is
+        reached by nearest-neighbour lookup of the class indices."""
+        from .engine import default_slide_stride, slide_windows
+        B, _, H1, W1 = x.shape
+        (ch, cw), strd, origins = slide_windows(H1, W1, crop, stride if stride is not None else default_slide_stride(crop))
+        xs = torch.stack([x[:, :, y:y + ch, x0:x0 + cw] for y, x0 in origins], dim=1).reshape(B * len(origins), x.shape[1], ch, cw)
+        lo = self.model_forward(xs)
+        nc = self.model.num_classes if hasattr(self.model, 'num_classes') else lo.data.shape[1]
+        seg = torch.empty((B, H1, W1), dtype=torch.int64, device=lo.data.device)
+        hip.slide_argmax_confmat(lo, B, nc, H1, W1, (ch, cw), strd, None, -1, None, None, None, pred_out=seg)
+        H0, W0 = orig_hw
+        if (H0, W0) != (H1, W1):
+            iy = (torch.arange(H0, device=seg.device) * H1) // H0
+            ix = (torch.arange(W0, device=seg.device) * W1) // W0
+            seg = seg[:, iy][:, :, ix]
+        return seg.squeeze(0), self._colour(seg, orig_img, overlay)
+
+    def predict(self, image: torch.Tensor, overlay: bool = True, scales=None, flip: bool = False, slide=None):
         """image: uint8 CHW tensor (what torchvision.io.read_image returns).  -> (seg_map, colour image or None).
-        scales (e.g. (0.5, 0.75, 1.0, 1.25, 1.5, 1.75)) and / or flip: multi-scale + flip prediction (postprocess_msf); without
-        them the single forward of the reference."""
+        scales (e.g. (0.5, 0.75, 1.0, 1.25, 1.5, 1.75)) and / or flip: multi-scale + flip prediction (postprocess_msf); slide =
+        (crop, stride) (stride None: floor(2 crop / 3)): sliding-window prediction (predict_slide), not together with scales / flip;
+        without them the single forward of the reference."""
+        if slide is not None and (scales or flip):
+            raise ValueError('SemSeg.predict: slide together with scales / flip -- sliding windows at several scales or mirrored are '
+                             'not built')
         x = self.preprocess(image)
+        if slide is not None:
+            crop, stride = slide
+            return self.predict_slide(x, tuple(image.shape[1:]), crop, stride, image, overlay)
         if scales or flip:
             maps, flips = self.msf_maps(x, tuple(scales) if scales else (1.0,), bool(flip))
             return self.postprocess_msf(tuple(image.shape[1:]), maps, flips, image, overlay)

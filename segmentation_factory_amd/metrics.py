@@ -3,7 +3,9 @@
 ``hist`` stays an fp32 [n, n] tensor accumulated per batch (quirk Q5: exact only below 2**24 per cell), rows =
 ground truth.  Counting happens on device: ``update`` takes materialised NCHW logits like the reference;
 ``update_lowres`` takes the head output and fuses upsample + argmax + histogram in one kernel; ``update_msf`` takes the head outputs
-of one batch at several scales / mirrored (multi-scale + flip evaluation) and fuses resample + softmax + sum + argmax + histogram.
+of one batch at several scales / mirrored (multi-scale + flip evaluation) and fuses resample + softmax + sum + argmax + histogram;
+``update_slide`` takes the head outputs of the overlapping crops of one batch (sliding-window evaluation) and fuses resample + mean
+over the covering windows + argmax + histogram.
 """
 import torch
 import torch.distributed as dist
@@ -72,6 +74,18 @@ class Metrics:
         first = lowres_list[0]
         counts, flag, mat, target = self._count_targets(first.data.device, target, confmat)
         hip.msf_argmax_confmat(lowres_list, flips, first.B, n, H, W, target, self.ignore_label, mat, counts, flag)
+        hip.hist_accum_(self.hist, counts)
+
+    def update_slide(self, lowres_windows, target: torch.Tensor, size, crop, stride, confmat=None):
+        """Sliding-window counting: `lowres_windows` holds the head outputs of every crop x crop window of one batch (a TokenMap or a
+        (rows, h, w) tuple, image-major, then window order: hip.slide_grid / engine.slide_windows).  One kernel resamples every
+        covering window's map at each pixel of `size`, averages the logits, takes the arg max and counts -- the same static scratch, the
+        same hist_accum_ and the same one-pass feeding of both matrices as update_lowres; no full-resolution map exists."""
+        H, W = size
+        n = self.num_classes
+        data = lowres_windows.data if hasattr(lowres_windows, 'data') else lowres_windows[0]
+        counts, flag, mat, target = self._count_targets(data.device, target, confmat)
+        hip.slide_argmax_confmat(lowres_windows, target.numel() // (H * W), n, H, W, crop, stride, target, self.ignore_label, mat, counts, flag)
         hip.hist_accum_(self.hist, counts)
 
     def _finish(self, v):
