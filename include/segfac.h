@@ -820,6 +820,39 @@ typedef struct {
 } segf_input_sample;                                                     /* 72 bytes */
 int segf_input_train(const segf_input_sample* samples /*device [B]*/, int B, int H, int W, uint64_t* lsum_ws, const float* mean3,
                      const float* std3, const int64_t* label_lut, float* out_img, int64_t* out_lbl, void* stream);
+/* segf_input_train_scaled: the training protocol with scale augmentation,
+ *   ExtRandomScale((lo, hi)) -> ExtRandomCrop((H, W), pad_if_needed=True) -> ExtColorJitter -> ExtRandomHorizontalFlip -> ExtToTensor
+ *   -> ExtNormalize                                                  (datasets/extra_transform.py:75-96, 319-392 and as above)
+ * and the label table.  The caller draws the random values and does the size arithmetic (transforms.py `draw_scaled`): the source is
+ * resized to res_h x res_w -- Image.resize((res_w, res_h), BILINEAR) = ImagingResample's horizontal then vertical pass in 22-bit
+ * fixed point, each rounded and clipped to uint8; the label by Image.resize(..., NEAREST) = ImagingScaleAffine's index accumulated
+ * in double from output index 0 -- and the H x W crop window starts at (top, left) IN RESIZED COORDINATES, either of which may be
+ * negative (the border F.pad added).  Outside [0, res_h) x [0, res_w) the image reads 0 and the label `label_fill` (a raw uint8
+ * value, mapped through label_lut like any other).  Only the window is computed: no resized image and no horizontal-pass image
+ * exists; every crop pixel evaluates its vertical taps over horizontal-pass values formed on the fly (at most kmax x kmax source
+ * pixels), then the uint8 crops are staged in ws and segf_input_train's own kernels run over them (jitter, contrast mean over the
+ * crop with its padding, flip, float tail: the same bits).
+ * samples: HOST array [B] -- its values are checked on the host before anything is launched, then copied into ws on `stream`, and the
+ * stream is waited for before the kernels are queued, so the array may be reused on return (not capturable into a graph; the image /
+ * label pointers inside are device pointers and must outlive the kernels).  kmax >= every sample's tap count 2 * ceil(max(1, src /
+ * res)) + 1 on both axes.  ws: segf_input_train_scaled_ws(B, H, W, kmax) BYTES, 16-byte aligned; the size does not depend on any
+ * source or resized size.  SEGF_ERR_SHAPE, before any launch, for: a null pointer; out_img / out_lbl / ws not 16-byte aligned;
+ * res_h or res_w < 1 (or a source size < 1, a row stride shorter than a row); a sample that needs more than kmax taps; H * W > 2^30;
+ * |top| or |left| or a resized size > 2^30. */
+typedef struct {
+    const uint8_t* img;
+    const uint8_t* lbl;
+    int64_t img_stride, lbl_stride;
+    int32_t src_h, src_w, res_h, res_w;
+    int32_t top, left;
+    int32_t flip, order;
+    float factor[3];
+    int32_t label_fill;
+} segf_input_scaled_sample;                                              /* 80 bytes */
+int64_t segf_input_train_scaled_ws(int B, int H, int W, int kmax);
+int segf_input_train_scaled(const segf_input_scaled_sample* samples /*host [B]*/, int B, int H, int W, int kmax, void* ws,
+                            const float* mean3, const float* std3, const int64_t* label_lut, float* out_img, int64_t* out_lbl,
+                            void* stream);
 /* segf_input_val: ExtResize -> ExtToTensor -> ExtNormalize (build_datasets.py:24-29; extra_transform.py:395-419) for ONE image:
  * Image.resize((out_w, out_h), BILINEAR) = ImagingResample's horizontal then vertical pass in 22-bit fixed point, each rounded to
  * uint8, and Image.resize(..., NEAREST) for the label (ImagingScaleAffine's accumulated source index); the caller computes

@@ -2,6 +2,8 @@
 // uint8 images that already live in HBM.
 //   train: ExtRandomCrop -> ExtColorJitter -> ExtRandomHorizontalFlip -> ExtToTensor -> ExtNormalize
 //          (datasets/build_datasets.py:14-22; datasets/extra_transform.py:319-392, 426-509, 196-214, 259-281, 288-313)
+//   train with scale augmentation: ExtRandomScale -> ExtRandomCrop(pad_if_needed) in front of the same stack
+//          (extra_transform.py:75-96, 319-392), the resize evaluated for the crop window only (segf_input_train_scaled)
 //   val:   ExtResize -> ExtToTensor -> ExtNormalize                      (build_datasets.py:24-29; extra_transform.py:395-419)
 // plus the label table + widening of the dataset classes (datasets/ade.py:122-124, cityscapes.py:159, coco_stuff.py:95-100).
 // The arithmetic is Pillow's (the transforms act on PIL images): ImagingBlend in C float with truncation / clipping, rgb2l =
@@ -180,7 +182,8 @@ __host__ __device__ inline int resample_ksize(int in_size, int out_size) {
 }
 
 // Resample.c precompute_coeffs + normalize_coeffs_8bpc (bilinear filter, support 1) for output index xx
-__device__ void coeffs_for(int xx, int in_size, int out_size, int ksize, int* __restrict__ bounds, int* __restrict__ kk) {
+// -> bounds2[0..1] = (first tap, tap count), kk[0..ksize) = this output index' own coefficients
+__device__ void coeffs_at(int xx, int in_size, int out_size, int ksize, int* __restrict__ bounds2, int* __restrict__ kk) {
     const double scale = (double)in_size / (double)out_size;
     const double fs = scale < 1.0 ? 1.0 : scale;
     const double support = 1.0 * fs, ss = 1.0 / fs;
@@ -204,10 +207,13 @@ __device__ void coeffs_for(int xx, int in_size, int out_size, int ksize, int* __
             w = a < 1.0 ? 1.0 - a : 0.0;
             if (ww != 0.0) w /= ww;
         }
-        kk[(int64_t)xx * ksize + x] = w < 0 ? (int)(-0.5 + w * (double)(1 << PRECISION_BITS)) : (int)(0.5 + w * (double)(1 << PRECISION_BITS));
+        kk[x] = w < 0 ? (int)(-0.5 + w * (double)(1 << PRECISION_BITS)) : (int)(0.5 + w * (double)(1 << PRECISION_BITS));
     }
-    bounds[2 * xx] = xmin;
-    bounds[2 * xx + 1] = xmax;
+    bounds2[0] = xmin;
+    bounds2[1] = xmax;
+}
+__device__ void coeffs_for(int xx, int in_size, int out_size, int ksize, int* __restrict__ bounds, int* __restrict__ kk) {
+    coeffs_at(xx, in_size, out_size, ksize, bounds + 2 * xx, kk + (int64_t)xx * ksize);
 }
 
 // Geometry.c ImagingScaleAffine (nearest): xo = a * 0.5; per output pixel xin = (int)xo; xo += a  (accumulated in double)
@@ -293,14 +299,162 @@ __global__ void __launch_bounds__(256) input_val_vpass_kernel(const uint8_t* __r
     }
 }
 
-}  // namespace
+// ---- training with scale augmentation: ExtRandomScale -> ExtRandomCrop(pad_if_needed) computed for the crop window only -----------
+// nearest_table's entry `idx` alone: the same chain of double additions from output index 0 (Pillow's bits), nothing stored on the way.
+// The first `uniform` (<= idx) of them are counted by a value that is the same for the whole workgroup: scalar loop control, no
+// divergence; only the remainder (< 256 for neighbouring lanes) differs by lane.
+__device__ int nearest_at(int n_in, int n_out, int idx, int uniform) {
+    const double a = (double)n_in / (double)n_out;
+    double xo = a * 0.5;
+#pragma unroll 8
+    for (int i = 0; i < uniform; ++i) xo += a;
+    for (int i = uniform; i < idx; ++i) xo += a;
+    const int v = (int)xo;
+    return v < 0 ? 0 : (v >= n_in ? n_in - 1 : v);
+}
 
-extern "C" int segf_input_train(const segf_input_sample* samples, int B, int H, int W, uint64_t* lsum_ws, const float* mean3,
-                                const float* std3, const int64_t* label_lut, float* out_img, int64_t* out_lbl, void* stream) {
-    if (B <= 0 || H <= 0 || W <= 0) return 0;
-    if (!samples || !lsum_ws || !mean3 || !std3 || !out_img || !out_lbl) return SEGF_ERR_SHAPE;
-    if ((int64_t)H * W > (int64_t)1 << 30) return SEGF_ERR_SHAPE;
-    if (((uintptr_t)out_img | (uintptr_t)out_lbl | (uintptr_t)lsum_ws | (uintptr_t)samples) % 16 != 0) return SEGF_ERR_SHAPE;
+// Workspace of segf_input_train_scaled, every part 16-byte aligned: the plain records and luma sums that the unchanged train kernels
+// read, the scaled records, per sample the tables of its W crop columns and H crop rows ([2W] column bounds, [W][kmax] column
+// coefficients, [2H] row bounds, [H][kmax] row coefficients, [W] + [H] nearest source indices), and the staged uint8 crops.
+struct ScaledWs {
+    segf_input_sample* recs; unsigned long long* lsum; segf_input_scaled_sample* srecs; int* tabs; uint8_t *img, *lbl;
+    int64_t per;                                                          // ints of one sample's tables
+};
+
+inline int64_t scaled_ws(void* ws, int B, int H, int W, int kmax, ScaledWs* t) {
+    auto up16 = [](int64_t v) { return (v + 15) & ~(int64_t)15; };
+    const int64_t per = ((int64_t)(W + H) * (3 + kmax) + 3) & ~(int64_t)3;
+    const int64_t o_recs = 0, o_lsum = o_recs + up16((int64_t)B * sizeof(segf_input_sample)), o_srecs = o_lsum + up16((int64_t)B * 8),
+                  o_tabs = o_srecs + up16((int64_t)B * sizeof(segf_input_scaled_sample)), o_img = o_tabs + (int64_t)B * per * 4,
+                  o_lbl = o_img + up16((int64_t)B * H * W * 3), end = o_lbl + up16((int64_t)B * H * W);
+    if (t) {
+        uint8_t* p = (uint8_t*)ws;
+        t->recs = (segf_input_sample*)(p + o_recs); t->lsum = (unsigned long long*)(p + o_lsum);
+        t->srecs = (segf_input_scaled_sample*)(p + o_srecs); t->tabs = (int*)(p + o_tabs); t->img = p + o_img; t->lbl = p + o_lbl;
+        t->per = per;
+    }
+    return end;
+}
+
+struct ScaledTabs { int *hb, *hk, *vb, *vk, *nx, *ny; };
+__device__ __forceinline__ ScaledTabs scaled_tabs(const ScaledWs& t, int b, int H, int W, int kmax) {
+    int* p = t.tabs + (int64_t)b * t.per;
+    ScaledTabs r;
+    r.hb = p; r.hk = r.hb + 2 * W; r.vb = r.hk + (int64_t)W * kmax; r.vk = r.vb + 2 * H; r.nx = r.vk + (int64_t)H * kmax; r.ny = r.nx + W;
+    return r;
+}
+
+// one thread per crop column and crop row of a sample (grid.y = sample): crop column x is resized column left + x; outside the resized
+// image it has no taps.  Thread 0 also writes the plain record through which the train kernels read the staged crop.
+__global__ void __launch_bounds__(256) input_scale_tables_kernel(int H, int W, int kmax, ScaledWs t) {
+    const int b = blockIdx.y, g = blockIdx.x * 256 + threadIdx.x;
+    const segf_input_scaled_sample s = t.srecs[b];
+    const ScaledTabs tb = scaled_tabs(t, b, H, W, kmax);
+    if (g < W) {
+        const int rx = s.left + g, first = s.left + (int)blockIdx.x * 256;     // first: resized column of this workgroup's lane 0
+        int* hb = tb.hb + 2 * g;
+        if (rx >= 0 && rx < s.res_w) {
+            coeffs_at(rx, s.src_w, s.res_w, resample_ksize(s.src_w, s.res_w), hb, tb.hk + (int64_t)g * kmax);
+            tb.nx[g] = nearest_at(s.src_w, s.res_w, rx, first < 0 ? 0 : first);
+        } else {
+            hb[0] = 0; hb[1] = 0;
+            tb.nx[g] = 0;
+        }
+    }
+    if (g < H) {
+        const int ry = s.top + g, first_y = s.top + (int)blockIdx.x * 256;
+        int* vb = tb.vb + 2 * g;
+        if (ry >= 0 && ry < s.res_h) {
+            coeffs_at(ry, s.src_h, s.res_h, resample_ksize(s.src_h, s.res_h), vb, tb.vk + (int64_t)g * kmax);
+            tb.ny[g] = nearest_at(s.src_h, s.res_h, ry, first_y < 0 ? 0 : first_y);
+        } else {
+            vb[0] = 0; vb[1] = 0;
+            tb.ny[g] = 0;
+        }
+    }
+    if (g == 0) {
+        segf_input_sample r;
+        r.img = t.img + (int64_t)b * H * W * 3; r.lbl = t.lbl + (int64_t)b * H * W;
+        r.img_stride = (int64_t)W * 3; r.lbl_stride = W;
+        r.src_h = H; r.src_w = W; r.top = 0; r.left = 0;
+        r.flip = s.flip; r.order = s.order;
+        r.factor[0] = s.factor[0]; r.factor[1] = s.factor[1]; r.factor[2] = s.factor[2];
+        r.reserved = 0;
+        t.recs[b] = r;
+    }
+}
+
+__device__ __forceinline__ int clip8(int v) { v >>= PRECISION_BITS; return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// PX consecutive crop pixels per thread -> the staged uint8 crop.  A pixel inside the resized image is ImagingResample's vertical pass
+// over the horizontal-pass values of its (at most kmax) source rows, each of those formed here from its (at most kmax) source pixels
+// and rounded / clipped to uint8 as Pillow's intermediate image is; outside, the pad fill.  The tap loops are counted: a form with
+// the horizontal taps unrolled to a fixed 3 / 5 / 7 (absent taps re-reading tap 0 with coefficient 0) measured 1.3 - 1.55 x SLOWER --
+// the kernel is bound by the number of byte loads it issues, not by their latency.
+template <int PX>
+__global__ void __launch_bounds__(256) input_scale_crop_kernel(int H, int W, int kmax, ScaledWs t) {
+    const int b = blockIdx.y;
+    const segf_input_scaled_sample s = t.srecs[b];
+    const ScaledTabs tb = scaled_tabs(t, b, H, W, kmax);
+    uint8_t* oimg = t.img + (int64_t)b * H * W * 3;
+    uint8_t* olbl = t.lbl + (int64_t)b * H * W;
+    const int runs_per_row = W / PX, total = H * runs_per_row;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int y = idx / runs_per_row, x0 = (idx - y * runs_per_row) * PX;
+        const int ry = s.top + y;
+        int v[PX][3], l[PX];
+#pragma unroll
+        for (int k = 0; k < PX; ++k) { v[k][0] = 0; v[k][1] = 0; v[k][2] = 0; l[k] = s.label_fill & 255; }
+        if (ry >= 0 && ry < s.res_h) {
+            const int ymin = tb.vb[2 * y], nrow = tb.vb[2 * y + 1];
+            const int* kv = tb.vk + (int64_t)y * kmax;
+            const uint8_t* lrow = s.lbl + (int64_t)tb.ny[y] * s.lbl_stride;
+            int xmin[PX], ncol[PX], acc[PX][3];
+            bool in[PX];
+#pragma unroll
+            for (int k = 0; k < PX; ++k) {
+                const int rx = s.left + x0 + k;
+                in[k] = rx >= 0 && rx < s.res_w;
+                xmin[k] = tb.hb[2 * (x0 + k)]; ncol[k] = in[k] ? tb.hb[2 * (x0 + k) + 1] : 0;
+                acc[k][0] = acc[k][1] = acc[k][2] = 1 << (PRECISION_BITS - 1);
+            }
+            for (int j = 0; j < nrow; ++j) {
+                const uint8_t* prow = s.img + (int64_t)(ymin + j) * s.img_stride;
+                const int kvj = kv[j];
+#pragma unroll
+                for (int k = 0; k < PX; ++k) {
+                    const int* kh = tb.hk + (int64_t)(x0 + k) * kmax;
+                    const uint8_t* p = prow + (int64_t)xmin[k] * 3;
+                    int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
+                    for (int i = 0; i < ncol[k]; ++i) { const int c = kh[i]; s0 += p[3 * i] * c; s1 += p[3 * i + 1] * c; s2 += p[3 * i + 2] * c; }
+                    acc[k][0] += clip8(s0) * kvj; acc[k][1] += clip8(s1) * kvj; acc[k][2] += clip8(s2) * kvj;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < PX; ++k)
+                if (in[k]) {
+                    v[k][0] = clip8(acc[k][0]); v[k][1] = clip8(acc[k][1]); v[k][2] = clip8(acc[k][2]);
+                    l[k] = lrow[tb.nx[x0 + k]];
+                }
+        }
+        const int64_t pix = (int64_t)y * W + x0;
+        if (PX == 4) {                                     // W % 4 == 0: 12 image bytes at a multiple of 12, 4 label bytes at a multiple of 4
+            unsigned* o = reinterpret_cast<unsigned*>(oimg + pix * 3);
+            const unsigned d0 = v[0][0] | v[0][1] << 8 | v[0][2] << 16 | (unsigned)v[1][0] << 24,
+                           d1 = v[1][1] | v[1][2] << 8 | v[2][0] << 16 | (unsigned)v[2][1] << 24,
+                           d2 = v[2][2] | v[3][0] << 8 | v[3][1] << 16 | (unsigned)v[3][2] << 24;
+            o[0] = d0; o[1] = d1; o[2] = d2;
+            *reinterpret_cast<unsigned*>(olbl + pix) = l[0] | l[1] << 8 | l[2] << 16 | (unsigned)l[3] << 24;
+        } else {
+            oimg[pix * 3] = (uint8_t)v[0][0]; oimg[pix * 3 + 1] = (uint8_t)v[0][1]; oimg[pix * 3 + 2] = (uint8_t)v[0][2];
+            olbl[pix] = (uint8_t)l[0];
+        }
+    }
+}
+
+// the launches of segf_input_train (arguments already checked): zero the luma sums, sum, transform
+int launch_input_train(const segf_input_sample* samples, int B, int H, int W, uint64_t* lsum_ws, const float* mean3, const float* std3,
+                       const int64_t* label_lut, float* out_img, int64_t* out_lbl, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const bool px4 = W % 4 == 0;
     const int64_t runs = (int64_t)H * (px4 ? W / 4 : W);
@@ -319,6 +473,56 @@ extern "C" int segf_input_train(const segf_input_sample* samples, int B, int H, 
     }
     SEGF_CHECK_LAUNCH();
     return 0;
+}
+
+}  // namespace
+
+extern "C" int segf_input_train(const segf_input_sample* samples, int B, int H, int W, uint64_t* lsum_ws, const float* mean3,
+                                const float* std3, const int64_t* label_lut, float* out_img, int64_t* out_lbl, void* stream) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    if (!samples || !lsum_ws || !mean3 || !std3 || !out_img || !out_lbl) return SEGF_ERR_SHAPE;
+    if ((int64_t)H * W > (int64_t)1 << 30) return SEGF_ERR_SHAPE;
+    if (((uintptr_t)out_img | (uintptr_t)out_lbl | (uintptr_t)lsum_ws | (uintptr_t)samples) % 16 != 0) return SEGF_ERR_SHAPE;
+    return launch_input_train(samples, B, H, W, lsum_ws, mean3, std3, label_lut, out_img, out_lbl, stream);
+}
+
+extern "C" int64_t segf_input_train_scaled_ws(int B, int H, int W, int kmax) {
+    if (B <= 0 || H <= 0 || W <= 0 || kmax < 3 || (int64_t)H * W > (int64_t)1 << 30) return 0;
+    return scaled_ws(nullptr, B, H, W, kmax, nullptr);
+}
+
+extern "C" int segf_input_train_scaled(const segf_input_scaled_sample* samples, int B, int H, int W, int kmax, void* ws,
+                                       const float* mean3, const float* std3, const int64_t* label_lut, float* out_img,
+                                       int64_t* out_lbl, void* stream) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    if (!samples || !ws || !mean3 || !std3 || !out_img || !out_lbl) return SEGF_ERR_SHAPE;
+    if ((int64_t)H * W > (int64_t)1 << 30 || kmax < 3 || B > 65535) return SEGF_ERR_SHAPE;
+    if (((uintptr_t)out_img | (uintptr_t)out_lbl | (uintptr_t)ws) % 16 != 0) return SEGF_ERR_SHAPE;
+    const int big = 1 << 30;
+    for (int b = 0; b < B; ++b) {
+        const segf_input_scaled_sample& s = samples[b];
+        if (!s.img || !s.lbl || s.src_h < 1 || s.src_w < 1 || s.res_h < 1 || s.res_w < 1 || s.res_h > big || s.res_w > big)
+            return SEGF_ERR_SHAPE;
+        if (s.img_stride < (int64_t)s.src_w * 3 || s.lbl_stride < s.src_w) return SEGF_ERR_SHAPE;
+        if (s.top > big || s.top < -big || s.left > big || s.left < -big) return SEGF_ERR_SHAPE;
+        if (resample_ksize(s.src_h, s.res_h) > kmax || resample_ksize(s.src_w, s.res_w) > kmax) return SEGF_ERR_SHAPE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    ScaledWs t;
+    scaled_ws(ws, B, H, W, kmax, &t);
+    if (!segf_trace().dry) {
+        hipError_t e = hipMemcpyAsync(t.srecs, samples, (size_t)B * sizeof(segf_input_scaled_sample), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);                 // the caller's array is free again on return
+        if (e != hipSuccess) return (int)e;
+    }
+    const bool px4 = W % 4 == 0;
+    const int nt = W > H ? W : H;
+    hipLaunchKernelGGL(input_scale_tables_kernel, dim3((int)cdiv64(nt, 256), B), dim3(256), 0, st, H, W, kmax, t);
+    const int bx = (int)imin64(cdiv64((int64_t)H * (px4 ? W / 4 : W), 256), B >= 64 ? 64 : 1024);
+    if (px4) hipLaunchKernelGGL(input_scale_crop_kernel<4>, dim3(bx, B), dim3(256), 0, st, H, W, kmax, t);
+    else hipLaunchKernelGGL(input_scale_crop_kernel<1>, dim3(bx, B), dim3(256), 0, st, H, W, kmax, t);
+    SEGF_CHECK_LAUNCH();
+    return launch_input_train(t.recs, B, H, W, (uint64_t*)t.lsum, mean3, std3, label_lut, out_img, out_lbl, stream);
 }
 
 // ---- single-image inference (estimate_model.py:85-97): T.Resize((nH, nW)) on the uint8 CHW tensor + x / 255 + Normalize -----------

@@ -6,6 +6,7 @@ CPU fallback: if the shared library is missing, or a kernel returns non-zero, a 
 raised (the reference's own error convention is Python exceptions).
 """
 import ctypes as C
+import math
 import os
 import re
 
@@ -93,6 +94,9 @@ SegfPrepItem = _STRUCTS['SegfPrepItem']                 # one job of segf_prep_g
 SegfDwItem = _STRUCTS['SegfDwItem']                     # one layer of segf_gemm_dw_db_grouped
 SegfFinalizeItem = _STRUCTS['SegfFinalizeItem']         # one member of segf_colreduce_finalize_grouped
 InputSample = _STRUCTS['segf_input_sample']             # one image of segf_input_train (72 bytes)
+# one image of segf_input_train_scaled (80 bytes).  Kept under its own name, outside _STRUCTS: tests/test_host_cpu.py fixes the
+# membership of that table; tests/test_input_scale_cpu.py checks this record's layout against the C compiler the same way.
+InputScaledSample = _STRUCTS.pop('segf_input_scaled_sample')
 
 
 def lib():
@@ -1487,6 +1491,43 @@ def input_train(samples, B, H, W, mean3, std3, label_lut, out_img=None, out_lbl=
     lsum = torch.empty(max(B, 2), dtype=torch.int64, device=dev)
     _chk(lib().segf_input_train(_ptr(samples), B, H, W, _ptr(lsum), _ptr(mean3), _ptr(std3), _ptr(label_lut), _ptr(out_img),
                                 _ptr(out_lbl), _stream()), 'segf_input_train')
+    return out_img, out_lbl
+
+
+def resample_ksize(in_size, out_size):
+    """Taps per output pixel of Pillow's bilinear resample from `in_size` to `out_size` (csrc/input.hip resample_ksize)."""
+    return int(math.ceil(max(float(in_size) / float(out_size), 1.0))) * 2 + 1
+
+
+def _chk_arg(rc, name):
+    """As _chk, but the host-side refusal of an argument (SEGF_ERR_SHAPE, nothing launched) is a ValueError."""
+    if rc == ERR_SHAPE:
+        raise ValueError(f'{name} refused its arguments (SEGF_ERR_SHAPE); nothing was launched')
+    _chk(rc, name)
+
+
+def input_train_scaled(samples, B, H, W, kmax, mean3, std3, label_lut, out_img=None, out_lbl=None, ws=None):
+    """segf_input_train_scaled: `samples` = a HOST ctypes array of B InputScaledSample records (the library checks their values, then
+    uploads them itself; their image / label pointers must stay alive until the stream has run the kernels)
+    -> (fp32 [B, 3, H, W], int64 [B, H, W]).  ``ws``: a uint8 device tensor of segf_input_train_scaled_ws(B, H, W, kmax) bytes
+    (default: allocated here).  ValueError when the library refuses an argument."""
+    _need_cuda(mean3, std3, label_lut, out_img, out_lbl, ws)
+    assert isinstance(samples, C.Array) and samples._type_ is InputScaledSample and len(samples) == B
+    assert mean3.dtype == torch.float32 and std3.dtype == torch.float32 and mean3.numel() == 3 and std3.numel() == 3
+    assert label_lut is None or (label_lut.dtype == torch.int64 and label_lut.numel() == 256)
+    dev = mean3.device
+    if out_img is None:
+        out_img = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+    if out_lbl is None:
+        out_lbl = torch.empty((B, H, W), dtype=torch.int64, device=dev)
+    assert out_img.is_contiguous() and out_lbl.is_contiguous() and out_img.numel() == B * 3 * H * W and out_lbl.numel() == B * H * W
+    assert out_img.dtype == torch.float32 and out_lbl.dtype == torch.int64
+    need = int(lib().segf_input_train_scaled_ws(B, H, W, kmax))
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need
+    _chk_arg(lib().segf_input_train_scaled(C.cast(samples, C.c_void_p), B, H, W, kmax, _ptr(ws), _ptr(mean3), _ptr(std3),
+                                           _ptr(label_lut), _ptr(out_img), _ptr(out_lbl), _stream()), 'segf_input_train_scaled')
     return out_img, out_lbl
 
 

@@ -14,6 +14,10 @@ The RANDOM DRAWS stay on the host and follow the reference's call order on Pytho
 (extra_transform.py:342-360), ExtColorJitter.get_params (:470-497: brightness, contrast, saturation factor, then
 ``random.shuffle``), ExtRandomHorizontalFlip (:205-213) -- so that, with the same seed and the same decoded images, a batch equals
 what the reference's single-process loader yields.  No CPU fallback: the tensors must be device tensors.
+
+Scale augmentation (``DeviceTrainTransform(scale_range=, pad_if_needed=, label_fill=)``): ExtRandomScale (extra_transform.py:75-96)
+and ExtRandomCrop(pad_if_needed=True) (:378-385) in front of the same stack, `segf_input_train_scaled` -- Pillow's resize evaluated
+for the crop window only.
 """
 import random as _random
 
@@ -69,16 +73,37 @@ class _Base:
 
 class DeviceTrainTransform(_Base):
     """The training stack of build_datasets.py:14-22 for a whole batch.  ``rng``: a ``random.Random`` (default: the ``random``
-    module itself, as the reference uses it)."""
+    module itself, as the reference uses it).
+
+    With ``scale_range=(lo, hi)`` the stack becomes the training protocol with scale augmentation,
+        ExtCompose([ExtRandomScale((lo, hi)), ExtRandomCrop(size, pad_if_needed=...), ExtColorJitter, ExtRandomHorizontalFlip, ...])
+    (extra_transform.py:75-96, 319-392): `draw_scaled` makes the draws and the size arithmetic, `segf_input_train_scaled` computes
+    the crop window of the resized image without ever forming that image.  ``label_fill``: the raw uint8 label value of the
+    border that ``pad_if_needed`` adds (the reference's F.pad fills 0; a training run wants its ignore label there).  Without
+    ``scale_range`` and ``pad_if_needed`` nothing changes."""
 
     def __init__(self, image_size, brightness=0.5, contrast=0.5, saturation=0.5, flip_p=0.5, mean=IMAGENET_MEAN, std=IMAGENET_STD,
-                 label_lut=None, device='cuda', rng=None):
+                 label_lut=None, device='cuda', rng=None, scale_range=None, pad_if_needed=False, label_fill=0):
         super().__init__(mean, std, label_lut, device)
         self.size = (int(image_size), int(image_size)) if isinstance(image_size, (int, float)) else tuple(int(v) for v in image_size)
         self.ranges = [(OP_BRIGHTNESS, _jitter_range(brightness)), (OP_CONTRAST, _jitter_range(contrast)),
                        (OP_SATURATION, _jitter_range(saturation))]
         self.flip_p = flip_p
         self.rng = rng if rng is not None else _random
+        if scale_range is not None:
+            scale_range = (float(scale_range[0]), float(scale_range[1]))
+            if not 0 < scale_range[0] <= scale_range[1]:
+                raise ValueError(f'scale_range {scale_range} should be 0 < lo <= hi')
+        if not 0 <= int(label_fill) <= 255:
+            raise ValueError(f'label_fill {label_fill} is not a uint8 label value')
+        self.scale_range, self.pad_if_needed, self.label_fill = scale_range, bool(pad_if_needed), int(label_fill)
+        self.scaled = scale_range is not None or self.pad_if_needed
+
+    def _jitter_flip(self):
+        ops = [(op, self.rng.uniform(r[0], r[1])) for op, r in self.ranges if r is not None]
+        self.rng.shuffle(ops)
+        flip = self.rng.random() < self.flip_p
+        return ops, bool(flip)
 
     def draw(self, src_h, src_w):
         """One sample's random values, drawn in the reference's order.  -> (top, left, [(op, factor), ...], flip)."""
@@ -88,10 +113,61 @@ class DeviceTrainTransform(_Base):
         else:
             top = self.rng.randint(0, abs(src_h - th))
             left = self.rng.randint(0, abs(src_w - tw))
-        ops = [(op, self.rng.uniform(r[0], r[1])) for op, r in self.ranges if r is not None]
-        self.rng.shuffle(ops)
-        flip = self.rng.random() < self.flip_p
-        return top, left, ops, bool(flip)
+        ops, flip = self._jitter_flip()
+        return top, left, ops, flip
+
+    @staticmethod
+    def pad_border(res_h, res_w, th, tw):
+        """ExtRandomCrop.__call__ with pad_if_needed (extra_transform.py:378-385): F.pad with an int pads ALL FOUR borders, first
+        when the width is short, then -- on the already padded size -- when the height is.  -> the total border P."""
+        p = 0
+        if res_w < tw:
+            p = int((1 + tw - res_w) / 2)
+        if res_h + 2 * p < th:
+            p += int((1 + th - (res_h + 2 * p)) / 2)
+        return p
+
+    def draw_scaled(self, src_h, src_w):
+        """One sample's random values for the scaled stack, in the reference's order on the `random` stream: scale (:90), crop
+        row, crop column (:359-360; none when the padded size equals the crop), the jitter factors, the shuffle, the flip.
+        -> dict(scale, res_h, res_w, P, top, left, ops, flip, label_fill); (top, left) is the crop origin in the RESIZED image's
+        coordinates (crop origin in the padded image minus P) and may be negative."""
+        th, tw = self.size
+        scale = self.rng.uniform(self.scale_range[0], self.scale_range[1]) if self.scale_range is not None else None
+        res_h, res_w = (src_h, src_w) if scale is None else (int(src_h * scale), int(src_w * scale))      # :91
+        if res_h < 1 or res_w < 1:
+            raise ValueError(f'scale {scale} leaves nothing of a {src_h} x {src_w} image')
+        P = self.pad_border(res_h, res_w, th, tw) if self.pad_if_needed else 0
+        hp, wp = res_h + 2 * P, res_w + 2 * P
+        if wp == tw and hp == th:
+            i, j = 0, 0
+        else:
+            i = self.rng.randint(0, abs(hp - th))
+            j = self.rng.randint(0, abs(wp - tw))
+        ops, flip = self._jitter_flip()
+        # without pad_if_needed a crop that hangs over the edge reads 0 in the label too (Image.crop)
+        return dict(scale=scale, res_h=res_h, res_w=res_w, P=P, top=i - P, left=j - P, ops=ops, flip=flip,
+                    label_fill=self.label_fill if self.pad_if_needed else 0)
+
+    def pack_scaled(self, images, labels, params):
+        """-> (host array of segf_input_scaled_sample records, the largest tap count among them)."""
+        recs = (hip.InputScaledSample * len(images))()
+        kmax = 3
+        for k, (img, lbl, p) in enumerate(zip(images, labels, params)):
+            self._check(img, lbl)
+            r = recs[k]
+            r.img, r.lbl = img.data_ptr(), lbl.data_ptr()
+            r.img_stride, r.lbl_stride = img.stride(0), lbl.stride(0)
+            r.src_h, r.src_w, r.res_h, r.res_w = int(img.shape[0]), int(img.shape[1]), int(p['res_h']), int(p['res_w'])
+            r.top, r.left, r.flip, r.label_fill = int(p['top']), int(p['left']), int(p['flip']), int(p['label_fill'])
+            order = 0
+            for j, (op, f) in enumerate(p['ops']):
+                order |= op << (2 * j)
+                r.factor[j] = f
+            r.order = order
+            if r.res_h >= 1 and r.res_w >= 1:               # (anything else is the library's to refuse)
+                kmax = max(kmax, hip.resample_ksize(r.src_h, r.res_h), hip.resample_ksize(r.src_w, r.res_w))
+        return recs, kmax
 
     def pack(self, images, labels, params):
         recs = (hip.InputSample * len(images))()
@@ -113,11 +189,18 @@ class DeviceTrainTransform(_Base):
     def __call__(self, images, labels, params=None, out=None):
         """images: list of uint8 [h, w, 3] device tensors, labels: list of uint8 [h, w] -> (fp32 [B, 3, S, S], int64 [B, S, S]).
         ``params`` overrides the draws (one (top, left, ops, flip) per sample); ``out`` = (image, label) tensors to fill in place
-        (e.g. the input buffers of a captured train step: zero-copy feed)."""
+        (e.g. the input buffers of a captured train step: zero-copy feed).  With ``scale_range`` / ``pad_if_needed`` the draws
+        are `draw_scaled`'s dicts and the batch comes from `segf_input_train_scaled`."""
+        oi, ol = out if out is not None else (None, None)
+        if self.scaled:
+            if params is None:
+                params = [self.draw_scaled(int(i.shape[0]), int(i.shape[1])) for i in images]
+            recs, kmax = self.pack_scaled(images, labels, params)
+            return hip.input_train_scaled(recs, len(images), self.size[0], self.size[1], kmax, self.mean, self.std, self.label_lut,
+                                          oi, ol)
         if params is None:
             params = [self.draw(int(i.shape[0]), int(i.shape[1])) for i in images]
         samples = self.pack(images, labels, params)
-        oi, ol = out if out is not None else (None, None)
         return hip.input_train(samples, len(images), self.size[0], self.size[1], self.mean, self.std, self.label_lut, oi, ol)
 
 

@@ -157,7 +157,31 @@ def get_args_parser():
                         help='training batches from the device-side input pipeline (segmentation_factory_amd/transforms.py): the '
                              'decoded uint8 training set is uploaded once and the transform stack of datasets/build_datasets.py:14-22 '
                              'runs as HIP kernels')
+    parser.add_argument('--aug-scale', dest='aug_scale', nargs=2, type=float, default=None, metavar=('LO', 'HI'),
+                        help='--device-input: random rescaling of every training sample by a factor from [LO, HI] in front of the crop '
+                             '(ExtRandomScale, datasets/extra_transform.py:75-96); implies ExtRandomCrop(pad_if_needed=True)')
+    parser.add_argument('--aug-pad-label', dest='aug_pad_label', type=int, default=None,
+                        help='--aug-scale: raw label value of the padded border (default: --ignore_label, so that padding does not '
+                             'train as class 0)')
     return parser
+
+
+def check_aug_args(args):
+    """--aug-scale belongs to the device input pipeline: the DataLoader path runs the reference's own dataset transforms."""
+    if args.aug_scale is None:
+        if args.aug_pad_label is not None:
+            raise SystemExit('--aug-pad-label needs --aug-scale')
+        return
+    if not args.device_input:
+        raise SystemExit('--aug-scale needs --device-input: without it the batches come from the dataset classes of the reference, '
+                         'which apply their own transform stack')
+    lo, hi = args.aug_scale
+    if not 0 < lo <= hi:
+        raise SystemExit(f'--aug-scale {lo} {hi}: expected 0 < LO <= HI')
+    if args.aug_pad_label is None:
+        args.aug_pad_label = args.ignore_label
+    if not 0 <= args.aug_pad_label <= 255:
+        raise SystemExit(f'--aug-pad-label {args.aug_pad_label} is not a uint8 label value')
 
 
 class SyntheticSegDataset(Dataset):
@@ -225,7 +249,11 @@ def build_device_loader(args, train_set):
                 assert int(lbl.min()) >= 0 and int(lbl.max()) <= 255, 'label values must fit uint8 (255 = ignore)'
                 lbl = lbl.to(torch.uint8)
             ds.add(torch.as_tensor(np.asarray(img)), lbl)
-    tf = DeviceTrainTransform(args.image_size, device=args.device)
+    if args.aug_scale is not None:
+        tf = DeviceTrainTransform(args.image_size, device=args.device, scale_range=tuple(args.aug_scale), pad_if_needed=True,
+                                  label_fill=args.aug_pad_label)
+    else:
+        tf = DeviceTrainTransform(args.image_size, device=args.device)
     # seed 0 = the DistributedSampler of train_gpu.py:212-214 (constructed without a seed)
     return DeviceBatchLoader(ds, args.batch_size, tf, shuffle=True, seed=0, rank=utils.get_rank(), world=utils.get_world_size())
 
@@ -236,6 +264,7 @@ class _NullWriter:
 
 
 def main(args):
+    check_aug_args(args)
     print(args)
     utils.init_distributed_mode(args)
     writer = None
