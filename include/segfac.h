@@ -341,6 +341,17 @@ int segf_bn_cls_bwd_full(int dt, int64_t M, int C, int K, const void* dy, int64_
                          const float* mean, const float* rstd, const float* gamma, const float* beta, int act,
                          const float* chan_scale, int64_t rows_per_sample, int eval_mode, void* dx, float* dgamma, float* dbeta,
                          float* ws, const void* x1, int64_t ldx1, int C1, float* dG, float* dwcls, void* stream);
+/* segf_bn_cls_bwd_full with the classifier's BIAS gradient riding on pass 1 too: dbcls fp32 [K] = column sums of dy, added up from
+ * the dy tiles the workgroups of the first feature slice stage anyway (fixed order: deterministic; a different order than
+ * segf_colsum's, so dbcls differs from it in round-off).  dwcls and dbcls are both required; every other output has the bits of
+ * segf_bn_cls_bwd_full.  _supported: segf_bn_cls_bwd_supported and the policy SEGFAC_HEAD_DB_RIDE (1 = from 131072 rows on).
+ * ws >= segf_bn_cls_bwd_full_db_ws(M, C, K, rows_per_sample) floats. */
+int segf_bn_cls_bwd_full_db_supported(int dt, int64_t M, int C, int K, int64_t rows_per_sample);
+int64_t segf_bn_cls_bwd_full_db_ws(int64_t M, int C, int K, int64_t rows_per_sample);
+int segf_bn_cls_bwd_full_db(int dt, int64_t M, int C, int K, const void* dy, int64_t ldy, const void* w, int64_t ldw, const void* x,
+                            const float* mean, const float* rstd, const float* gamma, const float* beta, int act,
+                            const float* chan_scale, int64_t rows_per_sample, int eval_mode, void* dx, float* dgamma, float* dbeta,
+                            float* ws, const void* x1, int64_t ldx1, int C1, float* dG, float* dwcls, float* dbcls, void* stream);
 
 /* ---- Global Response Normalization (ConvNeXtV2 GRN, convnextv2.py:68-80) on NHWC rows, B images of rows_per_sample rows:
  * y = gamma * (x * Nx) + beta + x, Nx = ||x||_2(H,W) / (mean_c ||x||_2 + 1e-6).  sumsq_out [B][C] is saved for the backward.
@@ -473,6 +484,12 @@ int segf_dwconv3x3_gelu_bwd_fc2_supported(int dt, int B, int H, int W, int C_hid
 int segf_dwconv3x3_gelu_bwd_fc2(int dt, int B, int H, int W, int C_hidden, int C_in, const void* f, const float* w9,
                                 const float* bias, const void* dys, int64_t ld_dys, const void* w2, void* du, void* dx,
                                 float* dw, float* db, float* ws, void* stream);
+/* The same call also takes C_in = 160 and 256 (MiT stages 3 and 4), where the W2 fragments no longer fit in registers: the four waves
+ * of a workgroup share one 64-channel slab and read the fragments from an LDS copy (dwconv3x3_walk_fc2_kernel<5>, <8>); same arithmetic
+ * per element, same bits.  Whether a step should take it is answered here and not by segf_dwconv3x3_gelu_bwd_fc2_supported, whose
+ * answers stay what they were (tests/test_ffn_bwd_fused_cpu.py holds it to 0 at C_in = 160 under every policy value): the same three conditions, with the row bound of policy value 1 chosen per C_in
+ * (profiles/ffn_bwd_stage34_ab.jsonl). */
+int segf_dwconv3x3_gelu_bwd_fc2_lds_supported(int dt, int B, int H, int W, int C_hidden, int C_in);
 
 /* ---- depthwise 7x7 conv + bias on NHWC (ConvNeXt Block.dwconv, convnext.py:29,39; convnextv2.py:88,101) --------------
  * wt: fp32 [49][C] (the [C][1][7][7] parameter transposed with segf_permute021); C % 8 == 0.                    */
@@ -924,6 +941,7 @@ int segf_input_val(const uint8_t* img, int64_t img_stride, const uint8_t* lbl, i
  *   SEGFAC_UPADD_GENERIC         upsample-add: the generic per-source kernels also for the 2-4-8 pyramid
  *   SEGFAC_NO_HEAD_FUSED         segf_bn_cls_bwd_supported answers 0: classifier data gradient and BatchNorm backward as separate passes
  *   SEGFAC_NO_HEAD_FUSED_DW      the folded head's stage-1 weight gradient does not ride on pass 2 of the fused BatchNorm backward
+ *   SEGFAC_HEAD_DB_RIDE          the classifier's bias gradient rides on pass 1 of the fused BatchNorm backward instead of a column-sum launch of its own (segf_bn_cls_bwd_full_db_supported): 0 = never, 1 = from 131072 token rows on, 2 = wherever the shape has the kernel  (default 1)
  *   SEGFAC_LOSS_NO_BAND          CE / Dice forward and backward on the tile kernels instead of the band sweep
  *   SEGFAC_LOSS_NO_BAND_FWD      ... the forward only
  *   SEGFAC_LOSS_BAND_ROWS        band sweep: rows per segment (0 = 16)

@@ -293,6 +293,15 @@ __global__ void __launch_bounds__(256, 2) dwconv3x3_walk_fc2_kernel(const bf16_t
                                                                      int64_t ld_dys, const bf16_t* __restrict__ w2,
                                                                      bf16_t* __restrict__ y, int B, int H, int W, int C, int R, int nseg) {
     typedef bf16_t T;
+    // KS > 2 (C_in = 160, 256: MiT stages 3 and 4): the 4 KS fragments no longer fit beside the walk's registers, so the four waves of a
+    // workgroup take the SAME 64 hidden channels on different pixel runs and read the fragments from one LDS copy (16 KS KB, staged once
+    // per workgroup in fragment order: one 16-byte LDS read per MFMA), and the dys rows run ONE row ahead of their use in two buffers
+    // instead of two rows ahead in three (the walk's sub-steps are unrolled six-fold there so that both rotations stay compile-time).
+    // At KS = 8 two buffers of 32 registers spill (256 VGPRs + 56 bytes of scratch): one buffer, loaded at the top of the sub-step that
+    // multiplies it after the 3 x 3 scatter.  gfx950: KS = 5 246 VGPRs, KS = 8 216 VGPRs, no scratch, two waves per SIMD.
+    constexpr bool WL = KS > 2;
+    constexpr int ND = KS > 5 ? 1 : (WL ? 2 : 3);                  // dys row buffers (KS = 8: the row is loaded in the sub-step that uses it)
+    constexpr int JU = ND == 2 ? 6 : 3;                            // sub-steps per trip of the walk loop
     const int lane = threadIdx.x & 63;
     const int n = lane & 15, g = lane >> 4;
     const int nslab = C / 64;
@@ -300,8 +309,10 @@ __global__ void __launch_bounds__(256, 2) dwconv3x3_walk_fc2_kernel(const bf16_t
     const int units = B * nseg * nrun;
     // wave-uniform bookkeeping lives in scalar registers
     const int wv = __builtin_amdgcn_readfirstlane((int)(xcd_block() * 4 + (threadIdx.x >> 6)));
-    const int ustep = (int)((gridDim.x * 4) / nslab);              // the launch makes the wave count a multiple of nslab
-    const int cbase = (wv % nslab) * 64;
+    // the launch makes the workgroup count a multiple of nslab
+    const int ustep = WL ? (int)(gridDim.x / nslab) * 4 : (int)((gridDim.x * 4) / nslab);
+    const int cbase = (WL ? (wv >> 2) % nslab : wv % nslab) * 64;
+    const int u0 = WL ? ((wv >> 2) / nslab) * 4 + (wv & 3) : wv / nslab;
     const int c0 = cbase + 4 * n;
     f32x2_t wk[9][2], bs[2];
 #pragma unroll
@@ -311,20 +322,36 @@ __global__ void __launch_bounds__(256, 2) dwconv3x3_walk_fc2_kernel(const bf16_t
         bs[jj] = bias ? f32x2_t{bias[c0 + 2 * jj], bias[c0 + 2 * jj + 1]} : f32x2_t{0.f, 0.f};
     }
     // W2 fragments: Bf[j][s] element e = w2[32 s + 8 g + e][c0 + j]
-    dwf_bf16x8 Bf[4][KS];
+    dwf_bf16x8 Bf[4][WL ? 1 : KS];
+    __shared__ dwf_u32x4 w2s[WL ? 4 * KS * 64 : 1];               // WL: fragment (j, s) of lane l at w2s[(j KS + s) 64 + l]
+    if constexpr (!WL) {
 #pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        dwf_s16x8 t[4];
+        for (int s = 0; s < KS; ++s) {
+            dwf_s16x8 t[4];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const uint2 q = *reinterpret_cast<const uint2*>(w2 + (int64_t)(32 * s + 8 * g + e) * C + c0);
-            t[0][e] = (short)(q.x & 0xffffu); t[1][e] = (short)(q.x >> 16); t[2][e] = (short)(q.y & 0xffffu); t[3][e] = (short)(q.y >> 16);
+            for (int e = 0; e < 8; ++e) {
+                const uint2 q = *reinterpret_cast<const uint2*>(w2 + (int64_t)(32 * s + 8 * g + e) * C + c0);
+                t[0][e] = (short)(q.x & 0xffffu); t[1][e] = (short)(q.x >> 16); t[2][e] = (short)(q.y & 0xffffu); t[3][e] = (short)(q.y >> 16);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) Bf[j][s] = __builtin_bit_cast(dwf_bf16x8, t[j]);
         }
+    } else {
+        for (int p = threadIdx.x; p < KS * 64; p += 256) {
+            const int s = p >> 6, l = p & 63;
+            dwf_s16x8 t[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) Bf[j][s] = __builtin_bit_cast(dwf_bf16x8, t[j]);
+            for (int e = 0; e < 8; ++e) {
+                const uint2 q = *reinterpret_cast<const uint2*>(w2 + (int64_t)(32 * s + 8 * (l >> 4) + e) * C + cbase + 4 * (l & 15));
+                t[0][e] = (short)(q.x & 0xffffu); t[1][e] = (short)(q.x >> 16); t[2][e] = (short)(q.y & 0xffffu); t[3][e] = (short)(q.y >> 16);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w2s[(j * KS + s) * 64 + l] = __builtin_bit_cast(dwf_u32x4, t[j]);
+        }
+        __syncthreads();
     }
-    const int steps = (R + 2 + 2) / 3;
-    for (int u = wv / nslab; u < units; u += ustep) {
+    const int steps = (R + 2 + JU - 1) / JU;
+    for (int u = u0; u < units; u += ustep) {
         const int run = u % nrun;
         const int t = u / nrun;
         const int seg = t % nseg;
@@ -350,7 +377,7 @@ __global__ void __launch_bounds__(256, 2) dwconv3x3_walk_fc2_kernel(const bf16_t
 #pragma unroll
             for (int p = 0; p < DW_PIX; ++p) { acc[a][p][0] = bs[0]; acc[a][p][1] = bs[1]; }
         Raw4<T> rawb[3][DW_PIX + 2];
-        dwf_u32x4 dysb[3][KS];                                    // rotating like the input rows: two rows ahead of their use
+        dwf_u32x4 dysb[ND][KS];                                   // rotating like the input rows: ND = 3 two rows ahead of their use, 2 one row, 1 none
         auto load_row = [&](int yin, Raw4<T> (&dst)[DW_PIX + 2]) {
             const int yc = yin < 0 ? 0 : (yin >= H ? H - 1 : yin);
             const T* row = xb + (int64_t)yc * W * C;
@@ -365,18 +392,19 @@ __global__ void __launch_bounds__(256, 2) dwconv3x3_walk_fc2_kernel(const bf16_t
         };
         load_row(ya - 1, rawb[0]);
         load_row(ya, rawb[1]);
-        load_grow(ya - 2, dysb[0]); load_grow(ya - 1, dysb[1]);
+        if constexpr (ND > 1) load_grow(ya - 2, dysb[0]);
+        if constexpr (ND > 2) load_grow(ya - 1, dysb[1]);
         int yin = ya - 1;
         for (int st = 0; st < steps; ++st) {
 #pragma unroll
-            for (int j = 0; j < 3; ++j, ++yin) {
+            for (int j = 0; j < JU; ++j, ++yin) {
                 f32x2_t (&P)[DW_PIX][2] = acc[j % 3];
                 f32x2_t (&Cc)[DW_PIX][2] = acc[(j + 1) % 3];
                 f32x2_t (&N)[DW_PIX][2] = acc[(j + 2) % 3];
                 Raw4<T> (&curc)[DW_PIX + 2] = rawb[j % 3];                // input row yin (loaded two sub-steps ago)
-                dwf_u32x4 (&gcurc)[KS] = dysb[j % 3];                     // dys row yin - 1
+                dwf_u32x4 (&gcurc)[KS] = dysb[j % ND];                    // dys row yin - 1
                 load_row(yin + 2, rawb[(j + 2) % 3]);
-                load_grow(yin + 1, dysb[(j + 2) % 3]);
+                load_grow(yin + ND - 2, dysb[(j + ND - 1) % ND]);
                 const bool vy = yin >= 0 && yin < H && yin <= yb;
 #pragma unroll
                 for (int cx = 0; cx < DW_PIX + 2; ++cx) {
@@ -403,8 +431,12 @@ __global__ void __launch_bounds__(256, 2) dwconv3x3_walk_fc2_kernel(const bf16_t
                     for (int jm = 0; jm < 4; ++jm) {
                         dgf[jm] = dwf_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                        for (int s = 0; s < KS; ++s)
-                            dgf[jm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(dwf_bf16x8, gcurc[s]), Bf[jm][s], dgf[jm], 0, 0, 0);
+                        for (int s = 0; s < KS; ++s) {
+                            dwf_bf16x8 bfr;
+                            if constexpr (WL) bfr = __builtin_bit_cast(dwf_bf16x8, w2s[(jm * KS + s) * 64 + lane]);
+                            else bfr = Bf[jm][s];
+                            dgf[jm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(dwf_bf16x8, gcurc[s]), bfr, dgf[jm], 0, 0, 0);
+                        }
                     }
                     T* orow = yo_b + (int64_t)yo * W * C;
 #pragma unroll
@@ -925,17 +957,32 @@ extern "C" int segf_dwconv3x3_bwd_blocks(int dt, int B, int H, int W, int C) {
 // kernels, the workspace and the deferred finalize (dw == NULL) are those of segf_dwconv3x3_gelu_bwd in its walk form.
 // Token rows from which policy value 1 takes the fused form (tools/bench_ffn_bwd.py, profiles/ffn_bwd_fused_ab.jsonl).
 #define DW_FC2_MIN_ROWS 131072
-static inline bool dw_fc2_shape_ok(int dt, int B, int H, int W, int C, int Cin) {
-    return dt == SEGF_BF16 && B > 0 && H > 0 && W > 0 && (Cin == 32 || Cin == 64) && C > 0 && C % 64 == 0 &&
+// C_in = 160, 256 (MiT stages 3 and 4): the kernel form with the W2 fragments in LDS; answered by segf_dwconv3x3_gelu_bwd_fc2_lds_supported.
+// A query of its own, because tests/test_ffn_bwd_fused_cpu.py holds segf_dwconv3x3_gelu_bwd_fc2_supported(bf16, 256, 32, 32, 640, 160) to 0
+// under the default policy AND under SEGFAC_FFN_BWD_FUSED = 2 (at batch 256 these maps are in the walk form, so no other condition makes
+// it 0): one query cannot say yes to that shape and keep that test.
+static inline bool dw_fc2_lds_cin(int Cin) { return Cin == 160 || Cin == 256; }
+static inline bool dw_fc2_shape_ok(int dt, int B, int H, int W, int C, int Cin, bool lds = false) {
+    return dt == SEGF_BF16 && B > 0 && H > 0 && W > 0 && (lds ? dw_fc2_lds_cin(Cin) : (Cin == 32 || Cin == 64)) && C > 0 && C % 64 == 0 &&
            (int64_t)B * H * W < (1ll << 31);
 }
-extern "C" int segf_dwconv3x3_gelu_bwd_fc2_supported(int dt, int B, int H, int W, int C_hidden, int C_in) {
-    if (!dw_fc2_shape_ok(dt, B, H, W, C_hidden, C_in)) return 0;
+static int dw_fc2_supported(int dt, int B, int H, int W, int C_hidden, int C_in, bool lds, int64_t min_rows) {
+    if (!dw_fc2_shape_ok(dt, B, H, W, C_hidden, C_in, lds)) return 0;
     if (!dw_use_walk() || dw_small_nch(dt, B, H, W, C_hidden)) return 0;        // the three-pass walk form must be the one in use
     const int pol = POL(ffn_bwd_fused);
     if (pol <= 0) return 0;
     if (pol >= 2) return 1;
-    return (int64_t)B * H * W >= DW_FC2_MIN_ROWS;
+    return (int64_t)B * H * W >= min_rows;
+}
+extern "C" int segf_dwconv3x3_gelu_bwd_fc2_supported(int dt, int B, int H, int W, int C_hidden, int C_in) {
+    return dw_fc2_supported(dt, B, H, W, C_hidden, C_in, false, DW_FC2_MIN_ROWS);
+}
+// Token rows from which policy value 1 takes the LDS form, per C_in (tools/bench_ffn_bwd.py, profiles/ffn_bwd_stage34_ab.jsonl)
+// measured: C_in = 160 wins from 16384 rows on (0.78 of the pair there); C_in = 256 0.89 at 32768 rows, 0.98 at 4096
+#define DW_FC2_LDS_MIN_ROWS_160 16384
+#define DW_FC2_LDS_MIN_ROWS_256 32768
+extern "C" int segf_dwconv3x3_gelu_bwd_fc2_lds_supported(int dt, int B, int H, int W, int C_hidden, int C_in) {
+    return dw_fc2_supported(dt, B, H, W, C_hidden, C_in, true, C_in == 160 ? DW_FC2_LDS_MIN_ROWS_160 : DW_FC2_LDS_MIN_ROWS_256);
 }
 extern "C" int segf_dwconv3x3_gelu_bwd_fc2(int dt, int B, int H, int W, int C_hidden, int C_in, const void* f, const float* w9,
                                            const float* bias, const void* dys, int64_t ld_dys, const void* w2, void* du, void* dx,
@@ -944,7 +991,7 @@ extern "C" int segf_dwconv3x3_gelu_bwd_fc2(int dt, int B, int H, int W, int C_hi
     const int C = C_hidden;
     if (dt != SEGF_BF16) return SEGF_ERR_DTYPE;
     // only where segf_dwconv3x3_gelu_bwd runs its three walk passes: segf_dwconv3x3_bwd_blocks then counts THIS call's partial blocks
-    if (!dw_fc2_shape_ok(dt, B, H, W, C, C_in) || !dw_use_walk() || dw_small_nch(dt, B, H, W, C)) return SEGF_ERR_SHAPE;
+    if (!dw_fc2_shape_ok(dt, B, H, W, C, C_in, dw_fc2_lds_cin(C_in)) || !dw_use_walk() || dw_small_nch(dt, B, H, W, C)) return SEGF_ERR_SHAPE;
     if (((uintptr_t)f % 16) || ((uintptr_t)dys % 16) || ((uintptr_t)w2 % 16) || ((uintptr_t)du % 16) || ((uintptr_t)dx % 16) ||
         ld_dys < C_in || ld_dys % 8 != 0)
         return SEGF_ERR_SHAPE;
@@ -959,7 +1006,19 @@ extern "C" int segf_dwconv3x3_gelu_bwd_fc2(int dt, int B, int H, int W, int C_hi
         int64_t blocks = (waves + 3) / 4;
         if (blocks > 32768) blocks = 32768;
         blocks = (blocks + nslab - 1) / nslab * nslab;          // whole groups of nslab waves: a wave keeps its channel slab (and its W2 fragments)
-        if (C_in == 32)
+        if (dw_fc2_lds_cin(C_in)) {
+            // LDS form: a WORKGROUP keeps its channel slab, its four waves take four units; nslab workgroups per group of four units
+            const int64_t units = (int64_t)B * q.nseg * ((W + 15) / 16);
+            int64_t groups = (units + 3) / 4;
+            if (groups * nslab > 32768) groups = 32768 / nslab;
+            blocks = groups * nslab;
+            if (C_in == 160)
+                hipLaunchKernelGGL((dwconv3x3_walk_fc2_kernel<5>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)f, w9, bias, (const T*)dys,
+                                   ld_dys, (const T*)w2, (T*)du, B, H, W, C, q.R, q.nseg);
+            else
+                hipLaunchKernelGGL((dwconv3x3_walk_fc2_kernel<8>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)f, w9, bias, (const T*)dys,
+                                   ld_dys, (const T*)w2, (T*)du, B, H, W, C, q.R, q.nseg);
+        } else if (C_in == 32)
             hipLaunchKernelGGL((dwconv3x3_walk_fc2_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)f, w9, bias, (const T*)dys,
                                ld_dys, (const T*)w2, (T*)du, B, H, W, C, q.R, q.nseg);
         else

@@ -444,12 +444,34 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
 __global__ void bernoulli_scale_kernel(uint64_t* __restrict__ state, const float* __restrict__ kp, int64_t n, int64_t row_len,
                                        float* __restrict__ out) {
     const uint64_t seed = state[0], ctr = state[1];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t r = splitmix64(splitmix64(seed ^ (ctr * 0xD1B54A32D192ED03ull)) + (uint64_t)i);
+    const uint64_t base = splitmix64(seed ^ (ctr * 0xD1B54A32D192ED03ull));
+    // out[i] is a pure function of i.  The table has at most 2^20 entries (checked by the launcher), so the indices are 32-bit and
+    // a row length past n means row 0 throughout.  A thread carries (row, position in row) of its element from trip to trip
+    // instead of a 64-bit i / row_len per element, and a trip issues BS_U independent kp loads before the first use: the division
+    // and the dependent load it fed used to serialise every element of the one workgroup.
+    constexpr uint32_t BS_U = 8;
+    const uint32_t nn = (uint32_t)n, rl = row_len < n ? (uint32_t)row_len : nn;
+    const uint32_t step = gridDim.x * blockDim.x;
+    const uint32_t srow = step / rl, srem = step - srow * rl;
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t row = i / rl, rem = i - row * rl;
+    auto advance = [&]() {
+        row += srow; rem += srem;
+        if (rem >= rl) { rem -= rl; ++row; }
+    };
+    auto scale = [&](uint32_t e, float k) {
+        const uint64_t r = splitmix64(base + (uint64_t)e);
         const float u = (float)(r >> 40) * (1.f / 16777216.f);
-        const float k = kp[i / row_len];
-        out[i] = u < k ? 1.f / k : 0.f;
+        return u < k ? 1.f / k : 0.f;
+    };
+    for (; (uint64_t)i + (uint64_t)(BS_U - 1) * step < nn; i += BS_U * step) {
+        float k[BS_U];
+#pragma unroll
+        for (uint32_t j = 0; j < BS_U; ++j) { k[j] = kp[row]; advance(); }
+#pragma unroll
+        for (uint32_t j = 0; j < BS_U; ++j) out[i + j * step] = scale(i + j * step, k[j]);
     }
+    for (; i < nn; i += step) { out[i] = scale(i, kp[row]); advance(); }
     __syncthreads();
     // the LAST workgroup to finish advances the counter (every workgroup has read it above): single-block launches in practice
     if (gridDim.x == 1 && threadIdx.x == 0) state[1] = ctr + 1;

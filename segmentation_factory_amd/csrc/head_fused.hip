@@ -33,6 +33,7 @@ struct HeadFusedArgs {
     const bf16_t* x1; int64_t ldx1;       // DW: [M][>= 32] second operand of the riding weight-gradient product
     float* dwpart;                        // DW: [gridDim.x / ny][C][DW_LD] per-workgroup partials of dx^T [x1 | 1]
     float* cwpart;                        // CW: [gridDim.x / ny][32 KS][C] per-workgroup partials of the classifier's weight gradient
+    float* dbpart;                        // DB: [gridDim.x][32 KS] per-workgroup partials of the classifier's bias gradient
 };
 #define DW_C1 32                          // channels of x1 (MiT-B0's stage-1 width)
 #define DW_LD 40                          // row length of the product: 32 channels, the all-ones column (= column sums of dx), 7 x 0
@@ -76,7 +77,14 @@ __device__ __forceinline__ float hf_row_sum16(float v) {
 // wave itself reads them back, so no workgroup barrier is added -- and multiplies dy^T (classes x tokens, transposed read of
 // the staged dy tile) with it: 2 KS x 2 accumulator tiles per wave, 4 KS MFMAs per 32 tokens.  Per-workgroup partials
 // [32 KS][C] are summed in fixed order by colreduce_finalize.
-template <int PASS, int KS, bool DW = false, bool CW = false>
+// DB (pass 1 only): the classifier's BIAS gradient db[class] = sum_tokens dy[token][class] rides along, instead of a column-sum launch
+// of its own over the M x 32 KS class gradients.  Every feature slice stages the same dy rows, so the slices take turns: tile i of
+// a chunk is summed by the workgroup of slice i % ny (with slice 0 alone, and the eight reads one after the other, the call kept most
+// of what it was to save; profiles/head_db_ride_ab.jsonl has the form below).  Of its staged 64-token tile wave w adds tokens
+// 8 w .. 8 w + 7, lane l classes 4 l .. 4 l + 3 (one 8-byte LDS read per token, four tokens at a time added as a tree), into four sums
+// of its own kept in LDS -- no register lives across the token loop.  The eight waves' sums are added as a fixed tree at the end;
+// per-workgroup partials [32 KS] are summed in fixed order by hf_db_finalize_kernel.  Rows of dead tail groups are skipped.
+template <int PASS, int KS, bool DW = false, bool CW = false, bool DB = false>
 __global__ void __launch_bounds__(64 * HF_WAVES, HF_OCC) bn_cls_bwd_kernel(HeadFusedArgs a) {
     constexpr int NT = 2;                                   // 32 features per wave
     constexpr int TOK = 16 * HF_U;                          // tokens per iteration
@@ -100,6 +108,8 @@ __global__ void __launch_bounds__(64 * HF_WAVES, HF_OCC) bn_cls_bwd_kernel(HeadF
     static_assert(!DW || (PASS == 2 && HF_WAVES == 8 && TOK == 64), "the riding weight gradient belongs to pass 2");
     static_assert(!CW || (PASS == 1 && TOK % 32 == 0), "the classifier's weight gradient rides on pass 1");
     __shared__ __attribute__((aligned(16))) bf16_t at[CW ? TOK : 1][XRS];
+    static_assert(!DB || (PASS == 1 && HF_WAVES == 8 && TOK == 64), "the classifier's bias gradient rides on pass 1");
+    __shared__ __attribute__((aligned(16))) float dbs[DB ? HF_WAVES : 1][DB ? 32 * KS : 4];
     hf_f32x4 accc[CW ? 2 * KS : 1][CW ? 2 : 1];
 #pragma unroll
     for (int i = 0; i < (CW ? 2 * KS : 1); ++i)
@@ -244,11 +254,41 @@ __global__ void __launch_bounds__(64 * HF_WAVES, HF_OCC) bn_cls_bwd_kernel(HeadF
     for (int i = 0; i < (DW ? 2 : 1); ++i)
 #pragma unroll
         for (int j = 0; j < (DW ? 3 : 1); ++j) accw[i][j] = hf_f32x4{0.f, 0.f, 0.f, 0.f};
+    const bool db_lane = DB && 4 * lane < 32 * KS;                         // lane's classes 4 lane .. 4 lane + 3 exist
+    if (DB) *reinterpret_cast<float4*>(&dbs[wave][db_lane ? 4 * lane : 0]) = make_float4(0.f, 0.f, 0.f, 0.f);   // own slot: no barrier
+    int db_turn = slice;                                                   // DB: tile i of the chunk is summed by slice i % ny
     if (gbeg < gend) { fetch_tile(gbeg); fetch_x(gbeg); fetch_x1(gbeg); stash_tile(0); stash_x(0); stash_x1(0, gbeg); }
     __syncthreads();
     int bufi = 0;
     for (int gp = gbeg; gp < gend; gp += HF_U) {
         const bool more = gp + HF_U < gend;
+        if (DB) {
+            // Ahead of the prefetch, while its staging registers are dead.  Tokens 8 wave .. 8 wave + 7 of the tile belong to group
+            // gp + (wave >> 1): wave-uniform liveness.  The eight reads are independent; the eight tokens are added as a tree.
+            const bool mine = db_turn == 0;
+            db_turn = mine ? ny - 1 : db_turn - 1;
+            if (mine && db_lane && gp + (wave >> 1) < gend) {
+                float4 h8 = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 1
+                for (int t0 = 0; t0 < 8; t0 += 4) {                    // four tokens at a time: the rider's registers stay few
+                    uint2 q[4];
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) q[t] = *reinterpret_cast<const uint2*>(&tile[bufi][8 * wave + t0 + t][4 * lane]);
+                    h8.x += (__uint_as_float(q[0].x << 16) + __uint_as_float(q[1].x << 16)) +
+                            (__uint_as_float(q[2].x << 16) + __uint_as_float(q[3].x << 16));
+                    h8.y += (__uint_as_float(q[0].x & 0xffff0000u) + __uint_as_float(q[1].x & 0xffff0000u)) +
+                            (__uint_as_float(q[2].x & 0xffff0000u) + __uint_as_float(q[3].x & 0xffff0000u));
+                    h8.z += (__uint_as_float(q[0].y << 16) + __uint_as_float(q[1].y << 16)) +
+                            (__uint_as_float(q[2].y << 16) + __uint_as_float(q[3].y << 16));
+                    h8.w += (__uint_as_float(q[0].y & 0xffff0000u) + __uint_as_float(q[1].y & 0xffff0000u)) +
+                            (__uint_as_float(q[2].y & 0xffff0000u) + __uint_as_float(q[3].y & 0xffff0000u));
+                }
+                float4 sv = *reinterpret_cast<const float4*>(&dbs[wave][4 * lane]);
+                sv.x += h8.x; sv.y += h8.y; sv.z += h8.z; sv.w += h8.w;
+                *reinterpret_cast<float4*>(&dbs[wave][4 * lane]) = sv;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
         if (more) { fetch_tile(gp + HF_U); fetch_x(gp + HF_U); fetch_x1(gp + HF_U); }
         constexpr int UNR = CW ? 1 : HF_U;                 // CW: 80 accumulator registers ride along -- one token group at a time
 #pragma unroll UNR
@@ -369,6 +409,14 @@ __global__ void __launch_bounds__(64 * HF_WAVES, HF_OCC) bn_cls_bwd_kernel(HeadF
 #pragma unroll
                 for (int r = 0; r < 4; ++r) dst[(int64_t)(16 * ct + 4 * g + r) * a.C + 16 * ft] = accc[ct][ft][r];
     }
+    if (DB) {
+        __syncthreads();
+        if ((int)threadIdx.x < 32 * KS) {
+            const int t = (int)threadIdx.x;
+            const float sv = ((dbs[0][t] + dbs[1][t]) + (dbs[2][t] + dbs[3][t])) + ((dbs[4][t] + dbs[5][t]) + (dbs[6][t] + dbs[7][t]));
+            a.dbpart[((int64_t)blk * ny + slice) * (32 * KS) + t] = sv;
+        }
+    }
     if (PASS == 1) {
         // tokens of a group sit in the 16 lanes of a row group: DPP row sums, then lane mi == 0 of each (wave, g) writes its 8 features
         float* dst = a.partial + (int64_t)blk * 2 * a.C + f0;
@@ -389,6 +437,23 @@ __global__ void hf_split_kernel(const float* __restrict__ sums, int C, float* __
     if (c >= C) return;
     dbeta[c] = sums[c];
     dgamma[c] = sums[C + c];
+}
+
+// DB: out[k] = sum over the nparts per-workgroup partials [nparts][K], one workgroup per class.  The partials are added in float64 (thread t
+// takes b = t, t + 256, ... ascending, then a fixed LDS tree) and rounded once: with colreduce_finalize's sixteen fp32 slice sums two rows
+// of +-1 among gradients of 1e-2 cost three times the round-off of the column-sum launch this replaces (tests/test_head_db_ride_gpu.py).
+__global__ void __launch_bounds__(256) hf_db_finalize_kernel(const float* __restrict__ part, int nparts, int K, float* __restrict__ out) {
+    __shared__ double red[256];
+    const int k = blockIdx.x;
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nparts; b += 256) s += (double)part[(int64_t)b * K + k];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[k] = (float)red[0];
 }
 
 static int hf_chunks(int B, int groups_per_sample, int ny, bool cw = false) {
@@ -435,7 +500,41 @@ extern "C" int64_t segf_bn_cls_bwd_dw_ws(int64_t M, int C, int64_t rows_per_samp
 static int bn_cls_bwd_impl(int dt, int64_t M, int C, int K, const void* dy, int64_t ldy, const void* w, int64_t ldw, const void* x,
                            const float* mean, const float* rstd, const float* gamma, const float* beta, int act,
                            const float* chan_scale, int64_t rows_per_sample, int eval_mode, void* dx, float* dgamma,
-                           float* dbeta, float* ws, const void* x1, int64_t ldx1, float* dG, void* stream, float* dwcls = nullptr);
+                           float* dbeta, float* ws, const void* x1, int64_t ldx1, float* dG, void* stream, float* dwcls = nullptr,
+                           float* dbcls = nullptr);
+
+// segf_bn_cls_bwd_full with the classifier's bias gradient dbcls fp32 [K] = column sums of dy riding on pass 1 as well (dwcls required:
+// the rider lives in the pass-1 form that carries the weight gradient).  Every other output has the bits of segf_bn_cls_bwd_full.
+#define HF_DB_MIN_ROWS 131072
+extern "C" int segf_bn_cls_bwd_full_db_supported(int dt, int64_t M, int C, int K, int64_t rows_per_sample) {
+    if (!segf_bn_cls_bwd_supported(dt, M, C, K, rows_per_sample)) return 0;
+    const int pol = POL(head_db_ride);
+    if (pol <= 0) return 0;
+    if (pol >= 2) return 1;
+    return M >= HF_DB_MIN_ROWS;
+}
+extern "C" int64_t segf_bn_cls_bwd_full_db_ws(int64_t M, int C, int K, int64_t rows_per_sample) {
+    const int B = (int)(M / rows_per_sample);
+    const int ny = C / (32 * HF_WAVES);
+    // the launch with dwcls lays its buffers out for the 768-workgroup plan; segf_bn_cls_bwd_full_ws is sized for the larger plan too, and
+    // the [nblk][ny][K] partials of the bias gradient usually fit behind the weight gradient's in what that leaves over (cfg2: no growth)
+    const int64_t nb = (int64_t)B * hf_chunks(B, (int)(rows_per_sample / 16), ny, true);
+    const int64_t used = nb * 2 * C + 2 * C + nb * C * DW_LD + nb * (int64_t)K * C + nb * ny * K;
+    const int64_t full = segf_bn_cls_bwd_full_ws(M, C, K, rows_per_sample);
+    return used > full ? used : full;
+}
+extern "C" int segf_bn_cls_bwd_full_db(int dt, int64_t M, int C, int K, const void* dy, int64_t ldy, const void* w, int64_t ldw,
+                                       const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int act,
+                                       const float* chan_scale, int64_t rows_per_sample, int eval_mode, void* dx, float* dgamma,
+                                       float* dbeta, float* ws, const void* x1, int64_t ldx1, int C1, float* dG, float* dwcls,
+                                       float* dbcls, void* stream) {
+    if (!segf_bn_cls_bwd_full_db_supported(dt, M, C, K, rows_per_sample) || !dwcls || !dbcls) return SEGF_ERR_SHAPE;
+    if (x1 && (!segf_bn_cls_bwd_dw_supported(dt, M, C, K, rows_per_sample, C1) || !dG || ldx1 < C1 || ldx1 % 8 || ((uintptr_t)x1 % 16)))
+        return SEGF_ERR_SHAPE;
+    if (K > 192 || act > 1) return SEGF_ERR_SHAPE;
+    return bn_cls_bwd_impl(dt, M, C, K, dy, ldy, w, ldw, x, mean, rstd, gamma, beta, act, chan_scale, rows_per_sample, eval_mode, dx,
+                           dgamma, dbeta, ws, x1, ldx1, x1 ? dG : nullptr, stream, dwcls, dbcls);
+}
 
 extern "C" int segf_bn_cls_bwd_full(int dt, int64_t M, int C, int K, const void* dy, int64_t ldy, const void* w, int64_t ldw,
                                     const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int act,
@@ -469,7 +568,7 @@ extern "C" int segf_bn_cls_bwd_dw(int dt, int64_t M, int C, int K, const void* d
 static int bn_cls_bwd_impl(int dt, int64_t M, int C, int K, const void* dy, int64_t ldy, const void* w, int64_t ldw, const void* x,
                            const float* mean, const float* rstd, const float* gamma, const float* beta, int act,
                            const float* chan_scale, int64_t rows_per_sample, int eval_mode, void* dx, float* dgamma,
-                           float* dbeta, float* ws, const void* x1, int64_t ldx1, float* dG, void* stream, float* dwcls) {
+                           float* dbeta, float* ws, const void* x1, int64_t ldx1, float* dG, void* stream, float* dwcls, float* dbcls) {
     if (!segf_bn_cls_bwd_supported(dt, M, C, K, rows_per_sample) || ldy < K || ldw < C || act < 0 || act > 2) return SEGF_ERR_SHAPE;
     if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx) % 16 || (ldy % 8)) return SEGF_ERR_SHAPE;
     if (!ws) return SEGF_ERR_WORKSPACE;
@@ -480,8 +579,9 @@ static int bn_cls_bwd_impl(int dt, int64_t M, int C, int K, const void* dy, int6
     float* sums = ws + (int64_t)nblk * 2 * C;
     float* dwpart = sums + 2 * C;                       // (only with x1) [nblk][C][DW_LD]
     float* cwpart = dwpart + (int64_t)nblk * C * DW_LD; // (only with dwcls) [nblk][K][C]
+    float* dbpart = cwpart + (int64_t)nblk * K * C;     // (only with dbcls) [nblk][ny][K]
     HeadFusedArgs a{(const bf16_t*)dy, ldy, (const bf16_t*)w, ldw, (const bf16_t*)x, mean, rstd, gamma, beta, chan_scale, sums,
-                    (bf16_t*)dx, ws, M, C, rows_per_sample, gps, chunks, act, eval_mode, (const bf16_t*)x1, ldx1, dwpart, cwpart};
+                    (bf16_t*)dx, ws, M, C, rows_per_sample, gps, chunks, act, eval_mode, (const bf16_t*)x1, ldx1, dwpart, cwpart, dbpart};
     const dim3 grid((unsigned)(nblk * ny));
 #define HF_LAUNCH(PASS)                                                                                                  \
     do {                                                                                                                 \
@@ -494,7 +594,20 @@ static int bn_cls_bwd_impl(int dt, int64_t M, int C, int K, const void* dy, int6
         default: hipLaunchKernelGGL((bn_cls_bwd_kernel<PASS, 6>), grid, dim3(64 * HF_WAVES), 0, st, a); break;                     \
         }                                                                                                                \
     } while (0)
-    if (dwcls) {
+    if (dwcls && dbcls) {
+        switch (K / 32) {
+        case 1: hipLaunchKernelGGL((bn_cls_bwd_kernel<1, 1, false, true, true>), grid, dim3(64 * HF_WAVES), 0, st, a); break;
+        case 2: hipLaunchKernelGGL((bn_cls_bwd_kernel<1, 2, false, true, true>), grid, dim3(64 * HF_WAVES), 0, st, a); break;
+        case 3: hipLaunchKernelGGL((bn_cls_bwd_kernel<1, 3, false, true, true>), grid, dim3(64 * HF_WAVES), 0, st, a); break;
+        case 4: hipLaunchKernelGGL((bn_cls_bwd_kernel<1, 4, false, true, true>), grid, dim3(64 * HF_WAVES), 0, st, a); break;
+        case 5: hipLaunchKernelGGL((bn_cls_bwd_kernel<1, 5, false, true, true>), grid, dim3(64 * HF_WAVES), 0, st, a); break;
+        default: hipLaunchKernelGGL((bn_cls_bwd_kernel<1, 6, false, true, true>), grid, dim3(64 * HF_WAVES), 0, st, a); break;
+        }
+        SEGF_CHECK_LAUNCH();
+        colreduce_finalize_launch(cwpart, nblk, (int64_t)K * C, dwcls, st);
+        SEGF_CHECK_LAUNCH();
+        hipLaunchKernelGGL(hf_db_finalize_kernel, dim3(K), dim3(256), 0, st, dbpart, nblk * ny, K, dbcls);
+    } else if (dwcls) {
         switch (K / 32) {
         case 1: hipLaunchKernelGGL((bn_cls_bwd_kernel<1, 1, false, true>), grid, dim3(64 * HF_WAVES), 0, st, a); break;
         case 2: hipLaunchKernelGGL((bn_cls_bwd_kernel<1, 2, false, true>), grid, dim3(64 * HF_WAVES), 0, st, a); break;

@@ -455,24 +455,53 @@ __global__ void __launch_bounds__(LS_THREADS) ce_dice_fwd_kernel(const T* __rest
 
 // stats[b][3C+4] (already summed over blocks) -> stats tail[4] at stats[B*(3C+4)], loss[3] = {total, ce, dice_loss}
 __global__ void __launch_bounds__(256) ce_dice_loss_kernel(float* __restrict__ stats, int B, int C, int dice, float* __restrict__ loss) {
+    // One workgroup: what it costs is load latency, so every trip issues its loads (LD_U elements x 3 here, a 256-sample chunk of
+    // the tails below) before the first use.  The additions keep their order: a thread adds its elements ascending, threads 0..3
+    // add the tails b ascending, then the same tree.
+    constexpr int LD_U = 8;
     __shared__ float red[256];
     __shared__ float tail[4];
+    __shared__ float tch[256 * 4];
     const int stride = 3 * C + 4;
+    const int n = B * C;
     float dsum = 0.f;
-    for (int i = threadIdx.x; i < B * C; i += 256) {
-        const int b = i / C, c = i - b * C;
-        const float* st = stats + (int64_t)b * stride;
-        const float I = st[c], P = st[C + c], T = st[2 * C + c];
+    auto term = [](float I, float P, float T) {
         float sets = P + T;
         if (sets == 0.f) sets = 2.f * I;
-        dsum += (2.f * I + LS_EPS) / (sets + LS_EPS);
+        return (2.f * I + LS_EPS) / (sets + LS_EPS);
+    };
+    int i = threadIdx.x;
+    for (; i + (LD_U - 1) * 256 < n; i += LD_U * 256) {
+        float I[LD_U], P[LD_U], T[LD_U];
+#pragma unroll
+        for (int j = 0; j < LD_U; ++j) {
+            const int e = i + j * 256, b = e / C, c = e - b * C;
+            const float* st = stats + (int64_t)b * stride;
+            I[j] = st[c]; P[j] = st[C + c]; T[j] = st[2 * C + c];
+        }
+#pragma unroll
+        for (int j = 0; j < LD_U; ++j) dsum += term(I[j], P[j], T[j]);
+    }
+    for (; i < n; i += 256) {
+        const int b = i / C, c = i - b * C;
+        const float* st = stats + (int64_t)b * stride;
+        dsum += term(st[c], st[C + c], st[2 * C + c]);
     }
     red[threadIdx.x] = dsum;
-    if (threadIdx.x < 4) {
-        float s = 0.f;
-        for (int b = 0; b < B; ++b) s += stats[(int64_t)b * stride + 3 * C + threadIdx.x];
-        tail[threadIdx.x] = s;
+    float s = 0.f;
+    for (int b0 = 0; b0 < B; b0 += 256) {
+        const int nb = B - b0 < 256 ? B - b0 : 256;
+        if (b0) __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int e = threadIdx.x + j * 256, b = e >> 2;
+            if (b < nb) tch[e] = stats[(int64_t)(b0 + b) * stride + 3 * C + (e & 3)];
+        }
+        __syncthreads();
+        if (threadIdx.x < 4)
+            for (int b = 0; b < nb; ++b) s += tch[b * 4 + threadIdx.x];
     }
+    if (threadIdx.x < 4) tail[threadIdx.x] = s;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];

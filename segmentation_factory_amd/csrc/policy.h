@@ -71,7 +71,8 @@
     X(upadd_generic, "SEGFAC_UPADD_GENERIC", 0, "upsample-add: the generic per-source kernels also for the 2-4-8 pyramid")               \
     X(no_head_fused, "SEGFAC_NO_HEAD_FUSED", 0, "segf_bn_cls_bwd_supported answers 0: classifier data gradient and BatchNorm backward as separate passes") \
     X(no_head_fused_dw, "SEGFAC_NO_HEAD_FUSED_DW", 0, "the folded head's stage-1 weight gradient does not ride on pass 2 of the fused BatchNorm backward") \
-    /* ---- loss / metrics (loss.hip, loss_band.hip) ---- */                                                                             \
+    X(head_db_ride, "SEGFAC_HEAD_DB_RIDE", 1, "the classifier's bias gradient rides on pass 1 of the fused BatchNorm backward instead of a column-sum launch of its own (segf_bn_cls_bwd_full_db_supported): 0 = never, 1 = from 131072 token rows on, 2 = wherever the shape has the kernel") \
+    /* ---- loss / metrics (loss.hip, loss_band.hip) ---- */                                                                            \
     X(loss_no_band, "SEGFAC_LOSS_NO_BAND", 0, "CE / Dice forward and backward on the tile kernels instead of the band sweep")            \
     X(loss_no_band_fwd, "SEGFAC_LOSS_NO_BAND_FWD", 0, "... the forward only")                                                             \
     X(loss_band_rows, "SEGFAC_LOSS_BAND_ROWS", 0, "band sweep: rows per segment (0 = 16)")                                               \

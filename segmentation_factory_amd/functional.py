@@ -1328,7 +1328,8 @@ def dwconv3x3_gelu_linear_ok(x, weight2, bias2, weight, bias, B, H, W):
         return False
     if bias is None or bias2 is None or not all(p.requires_grad for p in (weight2, bias2, weight, bias)):
         return False
-    return hip.dwconv3x3_gelu_bwd_fc2_supported(x.dtype, B, H, W, x.shape[1], weight2.shape[0])
+    return (hip.dwconv3x3_gelu_bwd_fc2_supported(x.dtype, B, H, W, x.shape[1], weight2.shape[0])
+            or hip.dwconv3x3_gelu_bwd_fc2_lds_supported(x.dtype, B, H, W, x.shape[1], weight2.shape[0]))
 
 
 def dwconv3x3_gelu_linear(x, weight2, bias2, weight, bias, B, H, W, residual=None, rscale=None):
@@ -1414,7 +1415,11 @@ class BnActLinearFn(Function):
         else:
             dyp = hip.zeros((M, Np), x.dtype, x.device)
             hip.cast2d(_rowmajor(dy), dyp[:, :N])
-        db = hip.colsum(dyp)[:N] if has_bias else None
+        # the bias gradient rides on pass 1 of the fused BatchNorm backward where that form carries the weight gradient too
+        # (segf_bn_cls_bwd_full_db): no column-sum pass of its own over the class gradients
+        ride_db = (has_bias and act in (0, 1) and not hip.policy('no_head_fused_cw')
+                   and hip.bn_cls_bwd_full_db_supported(x.dtype, M, K, Np, rps))
+        db = hip.colsum(dyp)[:N] if has_bias and not ride_db else None
         dw = None
         if hip.bn_cls_bwd_supported(x.dtype, M, K, Np, rps):
             # da = dyp W is recomputed inside both BatchNorm passes (K = #classes terms per element) instead of being written
@@ -1425,8 +1430,13 @@ class BnActLinearFn(Function):
             if act in (0, 1) and not hip.policy('no_head_fused_cw'):
                 # ... and the classifier's own weight gradient rides on the first pass (it has the x and dy tiles on chip), as the
                 # stage-1 weight gradient of the folded head rides on the second: no separate pass over x for either
-                dx, dg, dbeta, dG, dwc = hip.bn_cls_bwd_full(dyp, w, x, mean, rstd, g, b, act, chan_scale, rps, eval_mode,
-                                                             x1=x1 if ride_dg else None)
+                if ride_db:
+                    dx, dg, dbeta, dG, dwc, dbc = hip.bn_cls_bwd_full_db(dyp, w, x, mean, rstd, g, b, act, chan_scale, rps, eval_mode,
+                                                                         x1=x1 if ride_dg else None)
+                    db = dbc[:N]
+                else:
+                    dx, dg, dbeta, dG, dwc = hip.bn_cls_bwd_full(dyp, w, x, mean, rstd, g, b, act, chan_scale, rps, eval_mode,
+                                                                 x1=x1 if ride_dg else None)
                 dw = dwc[:N].view(wshape)
                 if ride_dg:
                     slot['dG'] = dG

@@ -979,6 +979,37 @@ def bn_cls_bwd_full(dy, w, x, mean, rstd, gamma, beta, act, chan_scale, rows_per
     return dx, dgamma, dbeta, dG, dwcls
 
 
+def bn_cls_bwd_full_db_supported(dtype, M, Cc, K, rps):
+    return dtype == torch.bfloat16 and bool(lib().segf_bn_cls_bwd_full_db_supported(BF16, M, Cc, K, rps))
+
+
+def bn_cls_bwd_full_db(dy, w, x, mean, rstd, gamma, beta, act, chan_scale, rows_per_sample, eval_mode, x1=None):
+    """bn_cls_bwd_full with the classifier's bias gradient dbcls fp32 [K] = colsum(dy) riding on pass 1 as well (segf_bn_cls_bwd_full_db;
+    act 0 / 1 only).  -> (dx, dgamma, dbeta, dG | None, dwcls, dbcls); all but dbcls have the bits of bn_cls_bwd_full."""
+    _need_cuda(dy, w, x)
+    M, Cc = x.shape
+    K = w.shape[0]
+    assert dy.shape[0] == M and dy.stride(1) == 1 and dy.stride(0) >= K and w.shape[1] == Cc and w.is_contiguous() and x.is_contiguous()
+    assert act in (0, 1)
+    dx = torch.empty_like(x)
+    dgamma = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    dG, C1 = None, 0
+    if x1 is not None:
+        assert x1.shape[0] == M and x1.stride(1) == 1 and x1.dtype == torch.bfloat16
+        C1 = x1.shape[1]
+        dG = torch.empty((Cc, C1 + 8), dtype=torch.float32, device=x.device)
+    dwcls = torch.empty((K, Cc), dtype=torch.float32, device=x.device)
+    dbcls = torch.empty(K, dtype=torch.float32, device=x.device)
+    ws = _f32(lib().segf_bn_cls_bwd_full_db_ws(M, Cc, K, rows_per_sample), x.device)
+    _chk(lib().segf_bn_cls_bwd_full_db(BF16, M, Cc, K, _ptr(dy), dy.stride(0), _ptr(w), w.stride(0), _ptr(x), _ptr(mean), _ptr(rstd),
+                                       _ptr(gamma), _ptr(beta), act, _ptr(chan_scale), rows_per_sample, int(eval_mode), _ptr(dx),
+                                       _ptr(dgamma), _ptr(dbeta), _ptr(ws), _ptr(x1) if x1 is not None else None,
+                                       x1.stride(0) if x1 is not None else 0, C1, _ptr(dG) if dG is not None else None,
+                                       _ptr(dwcls), _ptr(dbcls), _stream()), 'segf_bn_cls_bwd_full_db')
+    return dx, dgamma, dbeta, dG, dwcls, dbcls
+
+
 def grn_fwd(x, gamma, beta, B, rps, pre_gelu=False):
     Cc = x.shape[1]
     y = torch.empty_like(x)
@@ -1287,6 +1318,12 @@ def dwconv3x3_gelu_bwd_fc2_supported(dtype, B, H, W, Cc, Cin):
     """Does the Mix-FFN backward of this shape take the form that builds fc2's data gradient inside pass A (host arithmetic only)?"""
     dt = BF16 if dtype == torch.bfloat16 else F32
     return bool(lib().segf_dwconv3x3_gelu_bwd_fc2_supported(dt, B, H, W, Cc, Cin))
+
+
+def dwconv3x3_gelu_bwd_fc2_lds_supported(dtype, B, H, W, Cc, Cin):
+    """The same question for C_in = 160 / 256 (MiT stages 3 and 4), the kernel form with fc2's weight fragments in LDS."""
+    dt = BF16 if dtype == torch.bfloat16 else F32
+    return bool(lib().segf_dwconv3x3_gelu_bwd_fc2_lds_supported(dt, B, H, W, Cc, Cin))
 
 
 def dwconv3x3_gelu_bwd_fc2(x, w9, bias, dys, w2, B, H, W, Cc, Cin, dw_out=None, db_out=None, defer=False, return_du=False):

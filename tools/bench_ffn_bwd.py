@@ -1,6 +1,7 @@
 """Time the Mix-FFN backward tail at the SegFormer-B0 stage-1 / stage-2 shapes (bf16): the pair segf_gemm (fc2's data gradient, layout 1)
 + segf_dwconv3x3_gelu_bwd against the fused segf_dwconv3x3_gelu_bwd_fc2, alternating in one process.
 Usage: python tools/bench_ffn_bwd.py [--out profiles/ffn_bwd_fused_ab.jsonl] [--iters 40] [--batches 256 128 16 4]
+       python tools/bench_ffn_bwd.py --stage34 --batches 256 128 16 --out profiles/ffn_bwd_stage34_ab.jsonl     (stages 3 / 4: W2 fragments in LDS)
 
 One JSON line per shape: per-launch HIP-event times of both forms (median, min, max in microseconds), the ratio of the medians, and
 whether all of du / dx / dw / db came out bit-equal.  The clocks ramp for the first tens of milliseconds of load:
@@ -18,6 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segmentation_factory_amd import hip   # noqa: E402
 
 STAGES = [(128, 128, 128, 32), (64, 64, 256, 64)]          # (H, W, C_hidden, C_in) of MiT-B0 stages 1 and 2 at 512^2
+STAGES34 = [(32, 32, 640, 160), (16, 16, 1024, 256)]       # ... stages 3 and 4 (--stage34: W2 fragments in LDS, profiles/ffn_bwd_stage34_ab.jsonl)
 
 
 def one_shape(B, H, W, Cc, Cin, iters):
@@ -70,10 +72,14 @@ def one_shape(B, H, W, Cc, Cin, iters):
                 fn()
             kernels[name] = [k.split(' [')[0] for k in t.kernels]
     torch.cuda.synchronize()
-    stat = lambda v: {'median_us': round(statistics.median(v), 1), 'min_us': round(min(v), 1), 'max_us': round(max(v), 1)}     # noqa: E731
+    def stat(v):
+        q = statistics.quantiles(v, n=10)
+        return {'median_us': round(statistics.median(v), 1), 'p10_us': round(q[0], 1), 'p90_us': round(q[-1], 1), 'min_us': round(min(v), 1),
+                'max_us': round(max(v), 1)}
     return {'shape': [B, H, W, Cc, Cin], 'token_rows': M, 'launches_each': iters, 'pair': stat(times['pair']), 'fused': stat(times['fused']),
             'fused_over_pair': round(statistics.median(times['fused']) / statistics.median(times['pair']), 4), 'bit_equal': equal,
-            'supported_by_default': bool(lib.segf_dwconv3x3_gelu_bwd_fc2_supported(hip.BF16, B, H, W, Cc, Cin)),
+            'supported_by_default': bool(lib.segf_dwconv3x3_gelu_bwd_fc2_supported(hip.BF16, B, H, W, Cc, Cin)
+                                         or lib.segf_dwconv3x3_gelu_bwd_fc2_lds_supported(hip.BF16, B, H, W, Cc, Cin)),
             'pair_gemm_kernel': kernels['pair'][0], 'fused_kernel': kernels['fused'][0]}
 
 
@@ -82,10 +88,11 @@ def main():
     ap.add_argument('--out', default='')
     ap.add_argument('--iters', type=int, default=40)
     ap.add_argument('--batches', type=int, nargs='*', default=[256, 128, 16, 4])
+    ap.add_argument('--stage34', action='store_true', help='the stage-3 / stage-4 shapes instead of stages 1 / 2')
     a = ap.parse_args()
     lines = []
     for B in a.batches:
-        for (H, W, Cc, Cin) in STAGES:
+        for (H, W, Cc, Cin) in (STAGES34 if a.stage34 else STAGES):
             lines.append(json.dumps(one_shape(B, H, W, Cc, Cin, a.iters)))
             print(lines[-1], flush=True)
             torch.cuda.empty_cache()
