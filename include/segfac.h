@@ -810,6 +810,29 @@ int segf_flat_optim_step(int rule, float* param, const float* grad, float* s0, f
                          int nunits, float lr, float weight_decay, float h0, float h1, float eps, int nesterov,
                          float clip_factor, float agc_eps, void* stream);
 
+/* Per-group learning rate and weight decay (torch.optim parameter groups with their own `lr` / `weight_decay`: a decode head at
+ * 10 x the backbone's rate, layer-wise learning-rate decay, differential fine-tuning).  segf_agc_adamw_groups and
+ * segf_flat_optim_step_groups are segf_agc_adamw and segf_flat_optim_step -- the same kernel source, the same per-unit step counts,
+ * AGC on the raw gradient and per-rule arithmetic -- with the scalars `lr` / `weight_decay` replaced by
+ *   unit_group[u]  DEVICE uint8 [nunits]: the parameter group of unit u, < ngroups (a unit whose index is not is left untouched);
+ *   group_lr[g], group_wd[g]  HOST float [ngroups], 1 <= ngroups <= SEGF_OPT_MAX_GROUPS: read during the call and copied into a
+ *   by-value kernel argument (about 1 KB of kernarg), so the step stays ONE launch with launch scalars only -- no device table is
+ *   refreshed per step, no host-to-device copy that a host running ahead could race, and the arrays may be freed on return.
+ * Weight decay applies to unit u where group_wd[unit_group[u]] != 0; unit_flags bit 0 is IGNORED in the group forms, bit 1 (no
+ * gradient this step) keeps its meaning.  Status codes: SEGF_ERR_SHAPE, before any launch, for ngroups < 1, ngroups >
+ * SEGF_OPT_MAX_GROUPS, a null unit_group / group_lr / group_wd, and for whatever the scalar form of the rule refuses (a null buffer
+ * the rule needs, an unknown rule, Nesterov without momentum, step < 1 without unit_step); 0 on success (also for nunits <= 0); a
+ * positive hipError_t when the launch failed.  Measured against the scalar forms in profiles/optim_groups.md. */
+#define SEGF_OPT_MAX_GROUPS 128
+int segf_agc_adamw_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                          const int64_t* unit_offset, const int32_t* unit_len, const uint8_t* unit_flags, int32_t* unit_step,
+                          int nunits, const uint8_t* unit_group, int ngroups, const float* group_lr, const float* group_wd,
+                          float beta1, float beta2, float eps, int step, float clip_factor, float agc_eps, void* stream);
+int segf_flat_optim_step_groups(int rule, float* param, const float* grad, float* s0, float* s1,
+                                const int64_t* unit_offset, const int32_t* unit_len, const uint8_t* unit_flags, int32_t* unit_step,
+                                int nunits, const uint8_t* unit_group, int ngroups, const float* group_lr, const float* group_wd,
+                                float h0, float h1, float eps, int nesterov, float clip_factor, float agc_eps, void* stream);
+
 /* The other --clip-mode values of the reference (train_gpu.py:99-102 -> timm.utils.dispatch_clip_grad) on the flat gradient buffer:
  * mode 0 'norm' = torch.nn.utils.clip_grad_norm_(params, value, 2.0): g *= min(1, value / (||g||_2 + 1e-6));
  * mode 1 'value' = clip_grad_value_: g = clamp(g, -value, value).  ws: segf_clip_grad_ws() floats (mode 0).  No host read. */

@@ -424,6 +424,38 @@ def convnextv2_huge(**kw):
     return ConvNeXtV2(depths=[3, 3, 27, 3], dims=[352, 704, 1408, 2816], drop_path_rate=0.5, **kw)
 
 
+def layer_id_map(backbone):
+    """{parameter name (as in backbone.named_parameters()): layer id} for layer-wise learning-rate decay (optim.param_groups_lr_scale,
+    --layer-decay).  Id 0 is the stem (MiT's patch_embed1, ConvNeXt's downsample_layers.0); the blocks count from 1 in forward order
+    through the four stages; a stage's patch embedding / downsample layer takes the id of the first block it feeds; a stage-closing
+    normN takes the id of the stage's last block.  Whoever consumes the map puts the decode head at max(ids) + 1.  Built for the
+    families of the BASELINE configurations: MiT, ConvNeXt, ConvNeXtV2."""
+    if isinstance(backbone, MiT):
+        embed = lambda s: f'patch_embed{s + 1}.'
+        block = lambda s, j: f'block{s + 1}.{j}.'
+        norm = lambda s: f'norm{s + 1}.'
+    elif isinstance(backbone, _ConvNeXtBase):
+        embed = lambda s: f'downsample_layers.{s}.'
+        block = lambda s, j: f'stages.{s}.{j}.'
+        norm = lambda s: f'norm{s}.'
+    else:
+        raise ValueError(f'layer_id_map: no layer ids for the {type(backbone).__name__} family (built for MiT, ConvNeXt, ConvNeXtV2)')
+    prefix, first = {}, 1
+    for s, depth in enumerate(backbone.depths):
+        prefix[embed(s)] = 0 if s == 0 else first
+        for j in range(depth):
+            prefix[block(s, j)] = first + j
+        prefix[norm(s)] = first + depth - 1
+        first += depth
+    ids = {}
+    for name, _ in backbone.named_parameters():
+        hit = [i for p, i in prefix.items() if name.startswith(p)]
+        if len(hit) != 1:
+            raise ValueError(f'layer_id_map: parameter {name!r} of {type(backbone).__name__} belongs to no layer')
+        ids[name] = hit[0]
+    return ids
+
+
 # ---- MobileNetV2 (models/backbones/mobilenetv2.py) ------------------------------------------------------------------------
 def _bn_act(x, bn, training, act):
     """BatchNorm2d (+ReLU6) of mobilenetv2.ConvModule (mobilenetv2.py:5-11) / the bare BatchNorm2d of :29."""

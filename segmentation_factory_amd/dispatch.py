@@ -16,7 +16,8 @@ from . import hip
 # entry points that are not replayable (host-side struct arrays, events) or not dispatch decisions (queries, policy, trace)
 _SKIP_PREFIX = ('segf_policy', 'segf_trace', 'segf_event', 'segf_stream', 'segf_version', 'segf_debug', 'segf_gemm8_option')
 _SKIP = {'segf_prep_grouped', 'segf_colreduce_finalize_grouped', 'segf_input_train', 'segf_input_val', 'segf_infer_preprocess',
-         'segf_bernoulli_scale', 'segf_agc_adamw', 'segf_flat_optim_step', 'segf_clip_grad'}
+         'segf_bernoulli_scale', 'segf_agc_adamw', 'segf_flat_optim_step', 'segf_clip_grad', 'segf_agc_adamw_groups',
+         'segf_flat_optim_step_groups'}
 _PLACEHOLDER = 0x7f0000000000          # never dereferenced: dry runs skip every launch
 
 

@@ -1862,3 +1862,36 @@ def flat_optim_step(rule, param, grad, s0, s1, unit_off, unit_len, unit_flags, u
     _chk(lib().segf_flat_optim_step(OPT_RULES[rule], _ptr(param), _ptr(grad), _ptr(s0), _ptr(s1), _ptr(unit_off), _ptr(unit_len),
                                     _ptr(unit_flags), _ptr(unit_step), unit_len.numel(), lr, weight_decay, h0, h1, eps,
                                     int(bool(nesterov)), clip_factor, agc_eps, _stream()), 'segf_flat_optim_step')
+
+
+OPT_MAX_GROUPS = 128          # SEGF_OPT_MAX_GROUPS of include/segfac.h
+
+
+def _group_tables(group_lr, group_wd):
+    """(ngroups, host float arrays) of the per-group learning rates / weight decays: the library copies them into the kernel's
+    by-value argument at launch, so they are plain host memory that only has to live until the call returns."""
+    n = len(group_lr)
+    assert len(group_wd) == n
+    return n, (_f * max(n, 1))(*group_lr), (_f * max(n, 1))(*group_wd)
+
+
+def agc_adamw_groups(param, grad, exp_avg, exp_avg_sq, unit_off, unit_len, unit_flags, unit_group, group_lr, group_wd, beta1, beta2,
+                     eps, step, clip_factor, agc_eps=1e-3, unit_step=None):
+    """segf_agc_adamw_groups: segf_agc_adamw with the learning rate and weight decay of unit u taken from group unit_group[u]
+    (device uint8 [nunits]); group_lr / group_wd are host sequences of one value per group."""
+    _need_cuda(param, grad, exp_avg, exp_avg_sq, unit_off, unit_len, unit_flags, unit_group, unit_step)
+    n, lrs, wds = _group_tables(group_lr, group_wd)
+    _chk(lib().segf_agc_adamw_groups(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(unit_off), _ptr(unit_len),
+                                     _ptr(unit_flags), _ptr(unit_step), unit_len.numel(), _ptr(unit_group), n, lrs, wds, beta1, beta2,
+                                     eps, step, clip_factor, agc_eps, _stream()), 'segf_agc_adamw_groups')
+
+
+def flat_optim_step_groups(rule, param, grad, s0, s1, unit_off, unit_len, unit_flags, unit_step, unit_group, group_lr, group_wd, h0,
+                           h1=0.0, eps=0.0, nesterov=False, clip_factor=0.0, agc_eps=1e-3):
+    """segf_flat_optim_step_groups: segf_flat_optim_step with per-group learning rate and weight decay (see agc_adamw_groups)."""
+    _need_cuda(param, grad, s0, s1, unit_off, unit_len, unit_flags, unit_step, unit_group)
+    n, lrs, wds = _group_tables(group_lr, group_wd)
+    _chk(lib().segf_flat_optim_step_groups(OPT_RULES[rule], _ptr(param), _ptr(grad), _ptr(s0), _ptr(s1), _ptr(unit_off),
+                                           _ptr(unit_len), _ptr(unit_flags), _ptr(unit_step), unit_len.numel(), _ptr(unit_group), n,
+                                           lrs, wds, h0, h1, eps, int(bool(nesterov)), clip_factor, agc_eps, _stream()),
+         'segf_flat_optim_step_groups')

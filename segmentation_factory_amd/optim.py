@@ -9,6 +9,11 @@ The other --opt values (train_gpu.py:93-104,269: sgd / nesterov / momentum / ada
 segf_flat_optim_step.  Their ARITHMETIC is pinned: each rule is compared step for step with the torch.optim class of its name, which
 is installed (tests/test_optimizers_gpu.py).  The mapping from the --opt NAME to a class and its arguments is restated from timm
 0.9.2's create_optimizer_v2 and, like AGC, unpinned: timm is not available to compare against.
+
+Parameter groups may carry their own lr and weight_decay: the step is then the group form of the same kernels (segf_agc_adamw_groups /
+segf_flat_optim_step_groups: each unit looks its group's values up in a table that is a by-value kernel argument), pinned to torch.optim
+with the same groups (tests/test_optim_groups_gpu.py).  --head-lr-mult and --layer-decay build such groups (param_groups_lr_scale;
+the latter restates timm 0.9.2's param_groups_layer_decay: restated, not pinned).
 """
 import torch
 
@@ -28,7 +33,8 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
     FLAT_SLACK = 1024        # elements of zero padding behind the flat buffers (collective ranges round up to world x 16, graph.py)
     PARAM_ALIGN = 8          # every parameter starts at a multiple of this many elements in the flat buffers (_build)
     RULE = None              # name of the torch.optim class whose arithmetic and state_dict layout the subclass keeps
-    SHARED = ('lr',)         # hyper-parameters that are launch scalars of the one kernel: every group must agree on them
+    SHARED = ()              # hyper-parameters that are launch scalars of the one kernel: every group must agree on them
+    MAX_GROUPS = hip.OPT_MAX_GROUPS      # lr and weight_decay are per group: a table of this many entries is a kernel argument
     HAS_STEP = True          # the torch class keeps a per-parameter state['step']
     FIXED = {}               # group entries of the torch class that the kernel supports at one value only
 
@@ -38,6 +44,16 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
         self.direct = False
         self._step = 0
         self.agc_clip = 0.0          # set per step by NativeScaler when clip_mode == 'agc'
+        self.force_groups = False    # tests / tools: take the group form of the step kernel even where the scalar form would do
+
+    def add_param_group(self, param_group):
+        if getattr(self, '_flat', None) is not None:
+            raise RuntimeError(f'{type(self).__name__}.add_param_group: the flat buffers are built; their layout and the unit tables '
+                               'of the step kernel are fixed by the groups that existed then')
+        if len(self.param_groups) >= self.MAX_GROUPS:
+            raise ValueError(f'{type(self).__name__}: at most {self.MAX_GROUPS} parameter groups (SEGF_OPT_MAX_GROUPS: the per-group '
+                             'learning rates and weight decays are a fixed-size argument of the step kernel)')
+        super().add_param_group(param_group)
 
     def _state_spec(self, group):
         """[(state_dict key, attribute holding the flat state buffer)] under the hyper-parameters of `group`."""
@@ -52,12 +68,13 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
         """order: optional sequence of parameters (e.g. ``list(model.parameters())``) that fixes the LAYOUT of the flat buffers
         (registration order = reverse of the order in which backward finishes the gradients, so a suffix of the buffer is a
         bucket that completes early); default: parameter-group order.  The layout does not affect the arithmetic."""
-        ps, decay = [], {}
-        for g in self.param_groups:
+        ps, decay, group_of = [], {}, {}
+        for gi, g in enumerate(self.param_groups):
             for p in g['params']:
                 if p.requires_grad:
                     ps.append(p)
                     decay[id(p)] = g['weight_decay'] > 0
+                    group_of[id(p)] = gi
         if order is not None:
             rank = {id(p): i for i, p in enumerate(order)}
             ps.sort(key=lambda p: rank.get(id(p), len(rank)))
@@ -69,7 +86,7 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
         total = sum(self._spans)
         store = torch.zeros(total + self.FLAT_SLACK, dtype=torch.float32, device=dev)
         flat = store[:total]
-        offs, lens, flags = [], [], []
+        offs, lens, flags, ugroup = [], [], [], []
         o = 0
         for p, span in zip(ps, self._spans):
             d = decay[id(p)]
@@ -82,6 +99,7 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
                 offs.append(o + r * cols)
                 lens.append(cols)
                 flags.append(1 if d else 0)
+                ugroup.append(group_of[id(p)])
             o += span
         self._params = ps
         self._flat = flat
@@ -96,6 +114,7 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
         self._off = torch.tensor(offs, dtype=torch.int64, device=dev)
         self._len = torch.tensor(lens, dtype=torch.int32, device=dev)
         self._flags = torch.tensor(flags, dtype=torch.uint8, device=dev)
+        self._ugroup = torch.tensor(ugroup, dtype=torch.uint8, device=dev)      # each unit's parameter group (the group form of the step)
         # units (rows) of every parameter, for the per-step "received no gradient" bit (flag bit 1): torch.optim.AdamW -- the
         # reference's optimizer, train_gpu.py:269 -- skips a parameter whose .grad is None entirely (no decay, no moment update)
         self._unit_range, u = [], 0
@@ -215,17 +234,20 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
                 torch._foreach_zero_([self._grad_views[i] for i in missing])
 
     def _launch_scalars(self):
-        """(first group, the one non-zero weight decay).  One kernel runs over the flat buffer: the hyper-parameters are launch scalars
-        and weight decay is an on/off flag per unit, so every group must agree on them (timm's param_groups_weight_decay gives exactly
-        {0, wd}); anything else would be silently ignored."""
+        """(first group, the one non-zero weight decay, per-group tables).  One kernel runs over the flat buffer.  The hyper-parameters in
+        SHARED are its launch scalars, so every group must agree on them; anything else would be silently ignored.  lr and weight_decay
+        are per group.  Decided per step from the groups' current values (a scheduler may make them differ later): where all groups share
+        lr and the decays are {0, wd} (timm's param_groups_weight_decay) the tables are None and the step is the scalar kernel with
+        weight decay as the on/off flag per unit; otherwise they are ([lr per group], [weight decay per group]) for the group form."""
         g, name = self.param_groups[0], type(self).__name__
         for pg in self.param_groups[1:]:
             if any(_same(pg[k]) != _same(g[k]) for k in self.SHARED):
                 raise NotImplementedError(f'{name}: all parameter groups must share {" / ".join(self.SHARED)}')
         wds = {pg['weight_decay'] for pg in self.param_groups if pg['weight_decay'] > 0}
-        if len(wds) > 1:
-            raise NotImplementedError(f'{name}: one non-zero weight decay for all decayed groups, got {sorted(wds)}')
-        return g, max(pg['weight_decay'] for pg in self.param_groups)
+        tables = None
+        if self.force_groups or len(wds) > 1 or any(pg['lr'] != g['lr'] for pg in self.param_groups[1:]):
+            tables = ([float(pg['lr']) for pg in self.param_groups], [float(pg['weight_decay']) for pg in self.param_groups])
+        return g, max(pg['weight_decay'] for pg in self.param_groups), tables
 
     def _clip_front(self):
         """Launch the 'norm' / 'value' clipping of the flat gradient buffer, if set; returns the AGC factor for the step kernel (0 = off)."""
@@ -332,7 +354,7 @@ class FusedAGCAdamW(FusedFlatOptimizer):
     multi-tensor kernel (segf_agc_adamw).  Parameters are re-homed into one flat fp32 buffer (each
     ``p.data`` becomes a view), gradients are gathered into a flat buffer of the same layout."""
     RULE = 'AdamW'
-    SHARED = ('lr', 'betas', 'eps')
+    SHARED = ('betas', 'eps')
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -343,11 +365,15 @@ class FusedAGCAdamW(FusedFlatOptimizer):
     @torch.no_grad()
     def apply_flat(self):
         """AGC + AdamW over the flat buffers: one kernel launch (bias corrections are host scalars of this step)."""
-        g, wd = self._launch_scalars()
+        g, wd, tables = self._launch_scalars()
         self._step += 1
         agc = self._clip_front()
-        hip.agc_adamw(self._flat, self._grad, self._m, self._v, self._off, self._len, self._flags, g['lr'], g['betas'][0],
-                      g['betas'][1], g['eps'], wd, self._step, agc, unit_step=self._ustep)
+        if tables is None:
+            hip.agc_adamw(self._flat, self._grad, self._m, self._v, self._off, self._len, self._flags, g['lr'], g['betas'][0],
+                          g['betas'][1], g['eps'], wd, self._step, agc, unit_step=self._ustep)
+        else:
+            hip.agc_adamw_groups(self._flat, self._grad, self._m, self._v, self._off, self._len, self._flags, self._ugroup, *tables,
+                                 g['betas'][0], g['betas'][1], g['eps'], self._step, agc, unit_step=self._ustep)
 
     def load_state_dict(self, sd):
         """Accepts this class's own state_dict and a torch.optim.AdamW / timm AdamW one (the reference's checkpoints)."""
@@ -379,23 +405,30 @@ class FusedAGCAdamW(FusedFlatOptimizer):
 
 
 class _FlatRuleOptimizer(FusedFlatOptimizer):
-    """The rules of segf_flat_optim_step (csrc/optim.hip: flat_optim_kernel<RULE>)."""
+    """The rules of segf_flat_optim_step / segf_flat_optim_step_groups (csrc/optim.hip: flat_optim_kernel<RULE>, flat_optim_groups_kernel<RULE>).
+    A subclass names its rule (KERNEL_RULE) and maps a group's hyper-parameters to (s0, s1, the rule's keyword arguments) in _rule_args."""
 
     @torch.no_grad()
     def apply_flat(self):
-        g, wd = self._launch_scalars()
+        g, wd, tables = self._launch_scalars()
         self._alloc_state()
         self._step += 1
         agc = self._clip_front()
-        spec = [getattr(self, attr) for _, attr in self._state_spec(g)]
-        self._launch(g, wd, agc, spec)
+        s0, s1, kw = self._rule_args(g, [getattr(self, attr) for _, attr in self._state_spec(g)])
+        if tables is None:
+            hip.flat_optim_step(self.KERNEL_RULE, self._flat, self._grad, s0, s1, self._off, self._len, self._flags, self._ustep, g['lr'],
+                                wd, clip_factor=agc, **kw)
+        else:
+            hip.flat_optim_step_groups(self.KERNEL_RULE, self._flat, self._grad, s0, s1, self._off, self._len, self._flags, self._ustep,
+                                       self._ugroup, *tables, clip_factor=agc, **kw)
 
 
 class FusedSGD(_FlatRuleOptimizer):
     """torch.optim.SGD (momentum, optional Nesterov, dampening 0, weight decay coupled into the gradient) as one kernel over the
     flat buffers.  The momentum buffer starts at zero: torch clones the first gradient into it, which is momentum * 0 + g."""
     RULE = 'SGD'
-    SHARED = ('lr', 'momentum', 'nesterov')
+    SHARED = ('momentum', 'nesterov')
+    KERNEL_RULE = 'sgd'
     HAS_STEP = False
     FIXED = {'dampening': 0, 'maximize': False}
 
@@ -407,16 +440,16 @@ class FusedSGD(_FlatRuleOptimizer):
     def _state_spec(self, group):
         return [('momentum_buffer', '_buf')] if group['momentum'] != 0 else []
 
-    def _launch(self, g, wd, agc, bufs):
-        hip.flat_optim_step('sgd', self._flat, self._grad, bufs[0] if bufs else None, None, self._off, self._len, self._flags,
-                            self._ustep, g['lr'], wd, h0=g['momentum'], nesterov=g['nesterov'], clip_factor=agc)
+    def _rule_args(self, g, bufs):
+        return bufs[0] if bufs else None, None, dict(h0=g['momentum'], nesterov=g['nesterov'])
 
 
 class FusedAdam(_FlatRuleOptimizer):
     """torch.optim.Adam: AdamW's moments with the weight decay coupled into the gradient (L2) instead of decoupled."""
     RULE = 'Adam'
-    SHARED = ('lr', 'betas', 'eps')
+    SHARED = ('betas', 'eps')
     FIXED = {'amsgrad': False, 'maximize': False, 'decoupled_weight_decay': False}
+    KERNEL_RULE = 'adam'
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -424,16 +457,16 @@ class FusedAdam(_FlatRuleOptimizer):
     def _state_spec(self, group):
         return [('exp_avg', '_m'), ('exp_avg_sq', '_v')]
 
-    def _launch(self, g, wd, agc, bufs):
-        hip.flat_optim_step('adam', self._flat, self._grad, bufs[0], bufs[1], self._off, self._len, self._flags, self._ustep,
-                            g['lr'], wd, h0=g['betas'][0], h1=g['betas'][1], eps=g['eps'], clip_factor=agc)
+    def _rule_args(self, g, bufs):
+        return bufs[0], bufs[1], dict(h0=g['betas'][0], h1=g['betas'][1], eps=g['eps'])
 
 
 class FusedRMSprop(_FlatRuleOptimizer):
     """torch.optim.RMSprop (not centered), with its optional momentum buffer."""
     RULE = 'RMSprop'
-    SHARED = ('lr', 'alpha', 'eps', 'momentum')
+    SHARED = ('alpha', 'eps', 'momentum')
     FIXED = {'centered': False, 'maximize': False}
+    KERNEL_RULE = 'rmsprop'
 
     def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, momentum=0, weight_decay=0):
         super().__init__(params, dict(lr=lr, alpha=alpha, eps=eps, momentum=momentum, weight_decay=weight_decay, centered=False))
@@ -441,9 +474,8 @@ class FusedRMSprop(_FlatRuleOptimizer):
     def _state_spec(self, group):
         return [('square_avg', '_sq')] + ([('momentum_buffer', '_buf')] if group['momentum'] > 0 else [])
 
-    def _launch(self, g, wd, agc, bufs):
-        hip.flat_optim_step('rmsprop', self._flat, self._grad, bufs[0], bufs[1] if len(bufs) > 1 else None, self._off, self._len,
-                            self._flags, self._ustep, g['lr'], wd, h0=g['alpha'], h1=g['momentum'], eps=g['eps'], clip_factor=agc)
+    def _rule_args(self, g, bufs):
+        return bufs[0], bufs[1] if len(bufs) > 1 else None, dict(h0=g['alpha'], h1=g['momentum'], eps=g['eps'])
 
 
 class NativeScaler:
@@ -480,6 +512,40 @@ def param_groups_weight_decay(model, weight_decay):
     return [{'params': no_decay, 'weight_decay': 0.}, {'params': decay, 'weight_decay': weight_decay}]
 
 
+def param_groups_lr_scale(model, weight_decay, lr, head_lr_mult=1.0, layer_decay=None):
+    """Parameter groups with their own learning rate: timm's two weight-decay groups split further by `lr_scale`.
+
+    head_lr_mult M: parameters under ``decode_head.`` get lr_scale M (SegFormer's schedule trains the head at 10 x the backbone's
+    rate): up to four groups.  layer_decay D: timm 0.9.2's param_groups_layer_decay restated, not pinned (timm is not installed):
+    lr_scale = D ** (layer_max - layer_id) with a weight-decay and a no-decay group per layer; the layer ids of the backbone come from
+    backbones.layer_id_map, everything outside ``backbone.`` (the decode head) sits at layer_max, scale 1.  Both together multiply.
+
+    Every group carries 'lr_scale', 'lr' = lr * lr_scale (what the optimizer steps with until a scheduler writes the field) and
+    'initial_lr' = lr, the schedulers' base value: they write value * lr_scale (scheduler.Schedule.update_groups), so the scale is
+    applied once.  Groups are ordered by (layer, backbone before head, no-decay before decay); empty ones are left out."""
+    ids, layer_max = None, 0
+    if layer_decay is not None:
+        from .backbones import layer_id_map
+        ids = layer_id_map(model.backbone)
+        layer_max = max(ids.values()) + 1
+    groups = {}
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        head = name.startswith('decode_head.')
+        layer = layer_max
+        if ids is not None and name.startswith('backbone.'):
+            layer = ids[name[len('backbone.'):]]
+        scale = (1.0 if layer_decay is None else float(layer_decay) ** (layer_max - layer)) * (float(head_lr_mult) if head else 1.0)
+        decays = not (p.ndim <= 1 or name.endswith('.bias'))
+        key = (layer, head, decays)
+        if key not in groups:
+            groups[key] = {'params': [], 'weight_decay': weight_decay if decays else 0., 'lr': lr * scale, 'lr_scale': scale,
+                           'initial_lr': lr}
+        groups[key]['params'].append(p)
+    return [groups[k] for k in sorted(groups)]
+
+
 OPT_NAMES = ('adam', 'adamw', 'momentum', 'nesterov', 'rmsprop', 'sgd')
 
 
@@ -487,14 +553,20 @@ def create_optimizer(args, model):
     """timm.optim.create_optimizer(args, model) (train_gpu.py:269) for the --opt values that have a fused kernel here: the branch of
     timm 0.9.2's create_optimizer_v2 that each name reaches, over timm's weight-decay groups (no decay for 1-D tensors and biases).
     The name -> class / argument mapping is restated, not pinned (timm is not installed); the arithmetic of every class is pinned to
-    torch.optim.  `sgd` IS Nesterov in timm (`momentum` is the plain form); rmsprop gets alpha=0.9; the SGD forms drop --opt-eps."""
+    torch.optim.  `sgd` IS Nesterov in timm (`momentum` is the plain form); rmsprop gets alpha=0.9; the SGD forms drop --opt-eps.
+    --head-lr-mult / --layer-decay (args.head_lr_mult, args.layer_decay) split those groups by learning rate (param_groups_lr_scale);
+    with neither, the groups are exactly timm's two."""
     opt = str(getattr(args, 'opt', 'adamw')).lower()
     if opt not in OPT_NAMES:
         raise NotImplementedError(f"--opt {getattr(args, 'opt', None)}: the MI355X path has fused kernels for {', '.join(OPT_NAMES)} "
                                   "(the arithmetic of torch.optim's SGD / Adam / AdamW / RMSprop); timm's own optimizer classes are not implemented")
     wd = getattr(args, 'weight_decay', 0.025)
-    groups = param_groups_weight_decay(model, wd)
     lr, momentum = getattr(args, 'lr', 1e-3), getattr(args, 'momentum', 0.9)
+    head_mult, layer_decay = getattr(args, 'head_lr_mult', 1.0), getattr(args, 'layer_decay', None)
+    if head_mult == 1.0 and layer_decay is None:
+        groups = param_groups_weight_decay(model, wd)
+    else:       # --head-lr-mult / --layer-decay: groups with their own learning rate (the group form of the step kernels)
+        groups = param_groups_lr_scale(model, wd, lr, 1.0 if head_mult is None else head_mult, layer_decay)
     eps = getattr(args, 'opt_eps', None)
     betas = getattr(args, 'opt_betas', None)
     if opt in ('sgd', 'nesterov'):

@@ -76,6 +76,10 @@ def get_args_parser():
     parser.add_argument('--clip-mode', type=str, default='agc')
     parser.add_argument('--momentum', type=float, default=0.9, metavar='M', help='momentum of --opt sgd / nesterov / momentum / rmsprop')
     parser.add_argument('--weight-decay', type=float, default=0.025)
+    parser.add_argument('--head-lr-mult', type=float, default=1.0, metavar='M',
+                        help='learning rate of the decode head = M x --lr (SegFormer\'s schedule: 10); not a reference flag')
+    parser.add_argument('--layer-decay', type=float, default=None, metavar='D',
+                        help='layer-wise learning-rate decay: a layer\'s rate = --lr x D ** (layers above it); MiT / ConvNeXt / ConvNeXtV2; not a reference flag')
     # Learning rate schedule parameters (train_gpu.py:109-146)
     parser.add_argument('--sched', default='cosine', type=str, metavar='SCHEDULER')
     parser.add_argument('--lr', type=float, default=1e-3, metavar='LR')
