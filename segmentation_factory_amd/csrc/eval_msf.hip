@@ -4,14 +4,14 @@
 //   1.75, each also mirrored, every output is resized to the label size and softmaxed, the 2 S probability maps are summed and the
 //   arg max of the sum is scored.  Done with tensors that is 2 S full-resolution [C, H, W] fp32 maps plus an accumulator per image
 //   (157 MB each at C = 150, 512^2).  Here a pixel's class row of every map is resampled straight from the low-resolution NHWC rows
-//   (the arithmetic of the generic path of pixel_logits<T, NS, true> in loss.hip: bilinear_src + bilinear_aten), softmaxed across the
+//   (the arithmetic of the generic path of pixel_logits<T, NS, true> in loss_geom.h: bilinear_src + bilinear_aten), softmaxed across the
 //   lanes and added into per-lane fp32 accumulators; only the prediction / the counts (and, on request, the summed row) are written.
 // Layout of the work: classes on lanes, one GROUP of GW lanes per pixel -- GW = 64 with NS = ceil(C / 64) class slots per lane, or,
 // for C <= 32 / C <= 16, GW = 32 / 16 so that a wave carries 2 / 4 pixels (a 19-class row would otherwise leave 45 of 64 lanes idle
 // through every instruction).  A wave walks a contiguous pixel range of one image and loops over the maps per pixel, in map order:
 // S = p_0 + p_1 + ... is the same sequence of fp32 additions on every run, and nothing floating-point is accumulated across lanes
 // or workgroups except the fixed-shape butterfly of the softmax denominator -- two runs give the same bits.  Counts are integer
-// atomics (confmat_count of loss.hip).  The per-map descriptors travel BY VALUE in the kernel argument (MsfMaps, 512 bytes): no
+// atomics (eval_count of eval_rows.h).  The per-map descriptors travel BY VALUE in the kernel argument (MsfMaps, 512 bytes): no
 // device table, no upload, no host synchronisation, so the call can be captured into a hipGraph.
 #include "eval_rows.h"
 
@@ -30,14 +30,12 @@ __global__ void __launch_bounds__(MSF_THREADS) msf_argmax_confmat_kernel(MsfMaps
     static_assert(GW == 64 || NS == 1, "sub-wave groups hold one class per lane");
     constexpr int G = 64 / GW;                                   // pixels per wave and step
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = lane / GW, cl = lane - grp * GW;             // this lane's pixel of the step, its class (slot 0)
     const int b = blockIdx.y;
     const int64_t npix = (int64_t)H * W;
-    const int64_t nw = (int64_t)gridDim.x * (MSF_THREADS / 64);
-    const int64_t per = (npix + nw - 1) / nw;
-    const int64_t wid = (int64_t)blockIdx.x * (MSF_THREADS / 64) + wave;
-    const int64_t p0 = wid * per, p1 = p0 + per < npix ? p0 + per : npix;
+    static_assert(MSF_THREADS == 256, "wave_pixel_range: 4 waves per workgroup");
+    int64_t p0, p1;
+    wave_pixel_range(npix, p0, p1);
     const int64_t* tg = target ? target + (int64_t)b * npix : nullptr;
     const bool want_all = pred_out != nullptr || prob_out != nullptr;       // every pixel's row is needed, counted or not
     for (int64_t base = p0; base < p1; base += G) {

@@ -1,7 +1,16 @@
-// What the evaluation kernels with classes on lanes share (eval_msf.hip, eval_slide.hip): the reductions over a pixel's lane group,
-// the arg max of a class row spread over the group and the counting of one (label, prediction) pair.
+// What the evaluation kernels with classes on lanes share (eval_msf.hip, eval_slide.hip, and through loss_geom.h the arg max kernels
+// of loss.hip): a wave's slice of an image's pixels, the reductions over a pixel's lane group, the arg max of a class row spread over
+// the group and the counting of one (label, prediction) pair.
 #pragma once
 #include "common.h"
+
+// The pixels [p0, p1) of an image's npix that this wave walks: contiguous slices, 4 waves per workgroup, gridDim.x workgroups per image
+__device__ __forceinline__ void wave_pixel_range(int64_t npix, int64_t& p0, int64_t& p1) {
+    const int64_t nw = (int64_t)gridDim.x * 4;
+    const int64_t per = (npix + nw - 1) / nw;
+    const int64_t wid = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    p0 = wid * per; p1 = p0 + per < npix ? p0 + per : npix;
+}
 
 // reductions over the GW lanes of a pixel's group (every lane of the wave active); GW == 64: wave-uniform result
 template <int GW> __device__ __forceinline__ float grp_max(float v) { return GW == 64 ? wave_max_all(v) : wave_max(v, GW); }
@@ -25,8 +34,8 @@ template <int NS, int GW> __device__ __forceinline__ int grp_argmax(const float 
     return bi < C ? bi : 0;
 }
 
-// confmat_count of loss.hip for one pixel: mat at [t][best] where 0 <= t < C, hist the same except t == ignore_label; a label outside
-// [0, C) that is not ignore_label sets flag bit 0 and is counted nowhere
+// one pixel's count in both confusion matrices: mat at [t][best] where 0 <= t < C, hist the same except t == ignore_label; a label outside
+// [0, C) that is not ignore_label sets flag bit 0 and is counted nowhere (the reference's bincount shape check fails there)
 __device__ __forceinline__ void eval_count(int64_t t, int best, int C, int64_t ignore_label, unsigned long long* __restrict__ mat,
                                            unsigned long long* __restrict__ hist, int* __restrict__ flag) {
     const bool in_mat = t >= 0 && t < C;

@@ -29,14 +29,12 @@ __global__ void __launch_bounds__(SLIDE_THREADS) slide_argmax_confmat_kernel(con
     static_assert(GW == 64 || NS == 1, "sub-wave groups hold one class per lane");
     constexpr int G = 64 / GW;                                   // pixels per wave and step
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = lane / GW, cl = lane - grp * GW;             // this lane's pixel of the step, its class (slot 0)
     const int b = blockIdx.y;
     const int64_t npix = (int64_t)H * W;
-    const int64_t nw = (int64_t)gridDim.x * (SLIDE_THREADS / 64);
-    const int64_t per = (npix + nw - 1) / nw;
-    const int64_t wid = (int64_t)blockIdx.x * (SLIDE_THREADS / 64) + wave;
-    const int64_t p0 = wid * per, p1 = p0 + per < npix ? p0 + per : npix;
+    static_assert(SLIDE_THREADS == 256, "wave_pixel_range: 4 waves per workgroup");
+    int64_t p0, p1;
+    wave_pixel_range(npix, p0, p1);
     const int64_t* tg = target ? target + (int64_t)b * npix : nullptr;
     const bool want_all = pred_out != nullptr || mean_out != nullptr;       // every pixel's row is needed, counted or not
     const int64_t map_elems = (int64_t)h * w * ldl;                          // one window's map

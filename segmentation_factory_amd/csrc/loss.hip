@@ -14,145 +14,13 @@
 // backward recomputes the softmax per pixel and scatters d(logit) back onto the four taps through an LDS tile
 // (8x8 taps per workgroup, 9x9 cells incl. halo, four parity colours -> no atomics, bitwise reproducible), writing the
 // gradient of the LOW-resolution logits directly: no full-resolution tensor exists in either direction.
+// The class-row helpers of these kernels and the tile / parity-colour walk live in loss_geom.h, shared with loss_pixel.hip.
 // Non-power-of-two ratios fall back to the per-pixel kernels + segf_bilinear_bwd (still HIP).
 // Deterministic: per-block partials + fixed-order finalize, no float atomics.
 #include <stdlib.h>
 #include "colreduce.h"
 
 #include "loss_geom.h"
-
-static inline int pow2_scale(int h, int w, int H, int W) {
-    // sc >= 1 when H == sc*h, W == sc*w and sc is a power of two (exact source-index arithmetic); else 0
-    if (h <= 0 || w <= 0 || H % h || W % w) return 0;
-    const int sc = H / h;
-    if (W / w != sc || (sc & (sc - 1)) || sc > 8) return 0;   // sc*sc labels live one per lane
-    return sc;
-}
-
-// ---- per-lane class rows -------------------------------------------------------------------------------------
-template <typename T, int NS>
-__device__ __forceinline__ void load_tap(const T* __restrict__ p, int lane, int C, float (&t)[NS]) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {     // unconditional loads from a clamped index: all taps of a cell stay in flight together
-        const int c = lane + 64 * s;
-        const float v = ldf<T>(p + (c < C ? c : C - 1));
-        t[s] = c < C ? v : 0.f;
-    }
-}
-
-// z[s] = upsampled logit of class lane + 64*s at full-res pixel (Y, X); invalid class slots get -inf  (generic path)
-template <typename T, int NS, bool ATEN = false>
-__device__ __forceinline__ void pixel_logits(const T* __restrict__ img, const LossGeom& g, int Y, int X, int lane, float (&z)[NS]) {
-    if (g.h == g.H && g.w == g.W) {
-        const T* p = img + ((int64_t)Y * g.w + X) * g.ldl;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int c = lane + 64 * s;
-            const float v = ldf<T>(p + (c < g.C ? c : g.C - 1));
-            z[s] = c < g.C ? v : -INFINITY;
-        }
-        return;
-    }
-    int y0, y1, x0, x1; float ly, lx;
-    bilinear_src(Y, g.h, g.H, 0, y0, y1, ly);
-    bilinear_src(X, g.w, g.W, 0, x0, x1, lx);
-    const T* p00 = img + ((int64_t)y0 * g.w + x0) * g.ldl;
-    const T* p01 = img + ((int64_t)y0 * g.w + x1) * g.ldl;
-    const T* p10 = img + ((int64_t)y1 * g.w + x0) * g.ldl;
-    const T* p11 = img + ((int64_t)y1 * g.w + x1) * g.ldl;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const int c = lane + 64 * s, ci = c < g.C ? c : g.C - 1;
-        const float a = ldf<T>(p00 + ci), b = ldf<T>(p01 + ci), cc = ldf<T>(p10 + ci), d = ldf<T>(p11 + ci);
-        // ATEN (evaluation kernels): the operation order of the reference's CPU F.interpolate, so that arg max ties resolve alike
-        const float v = ATEN ? bilinear_aten(a, b, cc, d, ly, lx) : (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * cc + lx * d);
-        z[s] = c < g.C ? v : -INFINITY;
-    }
-}
-
-// softmax over the wave: p[s]; returns log-sum-exp (wave-uniform)
-template <int NS>
-__device__ __forceinline__ float wave_softmax(const float (&z)[NS], float (&p)[NS]) {
-    float mx = z[0];
-#pragma unroll
-    for (int s = 1; s < NS; ++s) mx = fmaxf(mx, z[s]);
-    mx = wave_max_all(mx);
-    float sum = 0.f;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) { p[s] = __expf(z[s] - mx); sum += p[s]; }
-    sum = wave_sum_all(sum);
-    const float inv = 1.f / sum;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) p[s] *= inv;
-    return mx + __logf(sum);
-}
-
-// softmax with a wave-uniform upper bound `mb` of max(z) in place of the exact maximum (every pixel of a cell is a convex
-// combination of the cell's four taps, so the taps' maximum bounds all of them: one wave reduction per CELL instead of
-// one per pixel).  Mathematically identical (softmax is shift invariant); if the bound is so loose that the sum
-// underflows, the exact-maximum path is taken instead (wave-uniform branch, practically never).
-template <int NS>
-__device__ __forceinline__ float wave_softmax_bounded(const float (&z)[NS], float mb, float (&p)[NS]) {
-    float sum = 0.f;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) { p[s] = __expf(z[s] - mb); sum += p[s]; }
-    sum = wave_sum_all(sum);
-    if (!(sum > 1e-30f)) return wave_softmax<NS>(z, p);
-    const float inv = 1.f / sum;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) p[s] *= inv;
-    return mb + __logf(sum);
-}
-template <int NS>
-__device__ __forceinline__ float cell_max_bound(const float (&t00)[NS], const float (&t01)[NS], const float (&t10)[NS],
-                                                const float (&t11)[NS], int lane, int C) {
-    float mx = -INFINITY;
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-        if (lane + 64 * s < C) mx = fmaxf(mx, fmaxf(fmaxf(t00[s], t01[s]), fmaxf(t10[s], t11[s])));
-    return wave_max_all(mx);
-}
-
-// A cell = the sc x sc full-res pixels between low-res taps (cj, ck) .. (cj+1, ck+1); cj in [-1, h-1] (taps clamp).
-struct Cell { int cj, ck, y0, y1, x0, x1; };
-__device__ __forceinline__ Cell make_cell(int cj, int ck, int h, int w, int halo) {
-    // halo == 0 (sc == 1, no resize): the cell is the pixel itself, all four taps coincide
-    Cell c; c.cj = cj; c.ck = ck;
-    c.y0 = cj < 0 ? 0 : cj; c.y1 = cj + halo > h - 1 ? h - 1 : cj + halo;
-    c.x0 = ck < 0 ? 0 : ck; c.x1 = ck + halo > w - 1 ? w - 1 : ck + halo;
-    return c;
-}
-template <typename T, int NS>
-__device__ __forceinline__ void load_cell_taps(const T* __restrict__ img, const LossGeom& g, const Cell& c, int lane,
-                                               float (&t00)[NS], float (&t01)[NS], float (&t10)[NS], float (&t11)[NS]) {
-    load_tap<T, NS>(img + ((int64_t)c.y0 * g.w + c.x0) * g.ldl, lane, g.C, t00);
-    load_tap<T, NS>(img + ((int64_t)c.y0 * g.w + c.x1) * g.ldl, lane, g.C, t01);
-    load_tap<T, NS>(img + ((int64_t)c.y1 * g.w + c.x0) * g.ldl, lane, g.C, t10);
-    load_tap<T, NS>(img + ((int64_t)c.y1 * g.w + c.x1) * g.ldl, lane, g.C, t11);
-}
-// fractional weight of pixel coordinate d inside its cell (exact for power-of-two sc; matches bilinear_src)
-__device__ __forceinline__ float cell_frac(int d, int in, int out) {
-    int i0, i1; float l;
-    bilinear_src(d, in, out, 0, i0, i1, l);
-    return l;
-}
-
-// Labels of the cell's sc x sc pixels, one per lane (lane = a * sc + bb), fetched with a single vector load:
-// code = class index, or -1 (skip: outside the image or equal to `skip_label`), or -2 (out-of-range label).
-__device__ __forceinline__ int cell_label_codes(const int64_t* __restrict__ tg, const LossGeom& g, int sc, int off, int cj, int ck,
-                                                int lane, int64_t skip_label, int64_t* raw = nullptr) {
-    int code = -1;
-    if (lane < sc * sc) {
-        const int a = lane / sc, bb = lane - a * sc;
-        const int Y = sc * cj + off + a, X = sc * ck + off + bb;
-        if (Y >= 0 && Y < g.H && X >= 0 && X < g.W) {
-            const int64_t t = tg[(int64_t)Y * g.W + X];
-            if (raw) *raw = t;
-            code = t == skip_label ? -1 : ((t < 0 || t >= g.C) ? -2 : (int)t);
-        }
-    }
-    return code;
-}
 
 // ---- forward: partial[blk][b][3C+4] = {I[C], P[C], T[C], ce_sum, w_sum, n_valid, bad} -------------------------------
 template <int NS>
@@ -397,7 +265,9 @@ __global__ void __launch_bounds__(LS_THREADS) ce_dice_fwd_cells_kernel(const T* 
                 float z[NS], pr[NS];
 #pragma unroll
                 for (int s = 0; s < NS; ++s) z[s] = (lane + 64 * s) < g.C ? (1.f - lx) * L[s] + lx * R[s] : -INFINITY;
-                const float lse = wave_softmax_bounded<NS>(z, mb, pr);
+                float shift;
+                const float lsum = wave_softmax_bounded<NS>(z, mb, pr, shift);
+                const float lse = shift + lsum;
                 const float wt = cw ? cw[t] : 1.f;
                 nvalid += 1.f; wsum += wt;
 #pragma unroll
@@ -422,10 +292,8 @@ __global__ void __launch_bounds__(LS_THREADS) ce_dice_fwd_kernel(const T* __rest
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.y;
     const int64_t npix = (int64_t)g.H * g.W;
-    const int64_t nw = (int64_t)gridDim.x * 4;
-    const int64_t per = (npix + nw - 1) / nw;
-    const int64_t wid = (int64_t)blockIdx.x * 4 + wave;
-    const int64_t p0 = wid * per, p1 = p0 + per < npix ? p0 + per : npix;
+    int64_t p0, p1;
+    wave_pixel_range(npix, p0, p1);
     const T* img = logits + (int64_t)b * g.h * g.w * g.ldl;
     const int64_t* tg = target + (int64_t)b * npix;
     float aI[NS], aP[NS], aT[NS];
@@ -439,7 +307,9 @@ __global__ void __launch_bounds__(LS_THREADS) ce_dice_fwd_kernel(const T* __rest
         const int Y = (int)(p / g.W), X = (int)(p - (int64_t)Y * g.W);
         float z[NS], pr[NS];
         pixel_logits<T, NS>(img, g, Y, X, lane, z);
-        const float lse = wave_softmax<NS>(z, pr);
+        float mx;
+        const float lsum = wave_softmax<NS>(z, pr, mx);
+        const float lse = mx + lsum;
         const float wt = cw ? cw[t] : 1.f;
         nvalid += 1.f; wsum += wt;
 #pragma unroll
@@ -517,33 +387,12 @@ __global__ void __launch_bounds__(256) ce_dice_loss_kernel(float* __restrict__ s
 }
 
 // ---- backward ----------------------------------------------------------------------------------------------------
-// d loss / d I and d loss / d P of the Dice term for this lane's classes
-template <int NS>
-__device__ __forceinline__ void dice_coefs(const float* __restrict__ stats, int b, int B, int C, int dice, int lane,
-                                           float (&gI)[NS], float (&gP)[NS]) {
-    const float* st = stats + (int64_t)b * (3 * C + 4);
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const int c = lane + 64 * s;
-        float a = 0.f, bb = 0.f;
-        if (c < C && dice) {
-            const float I = st[c], P = st[C + c], Tt = st[2 * C + c];
-            const float sets = P + Tt;
-            if (sets != 0.f) {   // sets == 0: d = (2I+eps)/(2I+eps) == 1 -> zero gradient
-                const float nbc = 1.f / (float)(B * C);
-                a = -nbc * 2.f / (sets + LS_EPS);
-                bb = nbc * (2.f * I + LS_EPS) / ((sets + LS_EPS) * (sets + LS_EPS));
-            }
-        }
-        gI[s] = a; gP[s] = bb;
-    }
-}
 // dz[s] = go * d loss / d z_c for one valid pixel with label t
 template <int NS>
 __device__ __forceinline__ void pixel_grad(const float (&z)[NS], int t, int lane, const float (&gI)[NS], const float (&gP)[NS],
                                            float wce, float go, float (&dz)[NS], float mb = INFINITY) {
-    float pr[NS], G[NS];
-    if (mb == INFINITY) wave_softmax<NS>(z, pr); else wave_softmax_bounded<NS>(z, mb, pr);
+    float pr[NS], G[NS], shift;
+    if (mb == INFINITY) wave_softmax<NS>(z, pr, shift); else wave_softmax_bounded<NS>(z, mb, pr, shift);
     float dot = 0.f;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -557,6 +406,9 @@ __device__ __forceinline__ void pixel_grad(const float (&z)[NS], int t, int lane
 }
 
 // Workgroup = LS_TILE x LS_TILE low-res taps of one image; it evaluates the (LS_TILE+1)^2 cells that touch them.
+// Its own copy of the walk that tile_cells_walk (loss_geom.h) holds for ce_dice_bwd_cells8_kernel: on the shared walk the
+// <float, 3> instantiation kept its resources but changed output bits (another choice of fused multiply-adds), see
+// profiles/loss_rows.md.  A change to the scatter or the store below belongs in tile_cells_walk too.
 template <typename T, int NS>
 __global__ void __launch_bounds__(LS_THREADS) ce_dice_bwd_cells_kernel(const T* __restrict__ logits, LossGeom g, int sc,
                                                                         const int64_t* __restrict__ target, int64_t ignore_index,
@@ -651,10 +503,10 @@ __global__ void __launch_bounds__(LS_THREADS) ce_dice_bwd_cells_kernel(const T* 
     }
 }
 
-// Batched backward, SC in {2, 4, 8}: same tile / colour structure as ce_dice_bwd_cells_kernel, but a cell's pixels are
-// processed 8 at a time in the exp2 domain with two transposing reductions per batch (sum of exponentials, <G, e>) instead
-// of three per-pixel reductions, branch-free pixel loops, and the tap scatter done separably (column weights per pixel,
-// row weights once per cell row).  A too-loose cell bound raises *retry; the exact kernel behind redoes the image set.
+// Batched backward, SC in {2, 4, 8}, on tile_cells_walk (loss_geom.h): a cell's pixels are processed 8 at a time in the exp2 domain with two transposing reductions
+// per batch (sum of exponentials, <G, e>) instead of three per-pixel reductions, branch-free pixel loops, and the tap scatter done
+// separably (column weights per pixel, row weights once per cell row).  A too-loose cell bound raises *retry; the exact kernel behind
+// redoes the image set.
 template <typename T, int NS, int SC>
 __global__ void __launch_bounds__(LS_THREADS, 4) ce_dice_bwd_cells8_kernel(const T* __restrict__ logits, LossGeom g,
                                                                             const int64_t* __restrict__ target, int64_t ignore_index,
@@ -669,131 +521,94 @@ __global__ void __launch_bounds__(LS_THREADS, 4) ce_dice_bwd_cells8_kernel(const
     constexpr int NB = SC * SC / NPB;
     constexpr int BPR = SC / COLS;
     constexpr int off = SC / 2;
-    __shared__ float accum[LS_TILE * LS_TILE][64 * NS];
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.y;
-    const int tiles_x = (g.w + LS_TILE - 1) / LS_TILE;
-    const int ty0 = (blockIdx.x / tiles_x) * LS_TILE, tx0 = (blockIdx.x % tiles_x) * LS_TILE;
-    for (int i = threadIdx.x; i < LS_TILE * LS_TILE * 64 * NS; i += LS_THREADS) (&accum[0][0])[i] = 0.f;
     float gI[NS], gP[NS];
     dice_coefs<NS>(stats, b, g.B, g.C, dice, lane, gI, gP);
     const float go = grad_out ? grad_out[0] : 1.f;
     const float invW = 1.f / stats[(int64_t)g.B * (3 * g.C + 4) + 1];
     const T* img = logits + (int64_t)b * g.h * g.w * g.ldl;
     const int64_t* tg = target + (int64_t)b * g.H * g.W;
-    __syncthreads();
-    constexpr int ncl = LS_TILE + 1;
-    for (int col = 0; col < 4; ++col) {
-        const int pj = col >> 1, pk = col & 1;
-        const int nj = (ncl - pj + 1) / 2, nk = (ncl - pk + 1) / 2;
-        for (int idx = wave; idx < nj * nk; idx += 4) {
-            const int lj = 2 * (idx / nk) + pj, lk = 2 * (idx % nk) + pk;
-            const int cj = ty0 - 1 + lj, ck = tx0 - 1 + lk;
-            if (cj > g.h - 1 || ck > g.w - 1) continue;
-            const Cell c = make_cell(cj, ck, g.h, g.w, 1);
-            float t00[NS], t01[NS], t10[NS], t11[NS], d0[NS], d1[NS], A00[NS], A01[NS], A10[NS], A11[NS];
-            load_cell_taps<T, NS>(img, g, c, lane, t00, t01, t10, t11);
-            const int codes = cell_label_codes(tg, g, SC, off, cj, ck, lane, ignore_index);      // -1 / -2: no gradient
-            const float mb = cell_max_bound<NS>(t00, t01, t10, t11, lane, g.C);
-            cell_scaled_taps<NS>(t00, t01, t10, t11, mb, lane, g.C, d0, d1);
-#pragma unroll
-            for (int s = 0; s < NS; ++s) { A00[s] = 0.f; A01[s] = 0.f; A10[s] = 0.f; A11[s] = 0.f; }
-            unsigned slow = 0;
+    tile_cells_walk<T, NS>(g, dlow, ldd, [&](int cj, int ck, const Cell& c, float (&A00)[NS], float (&A01)[NS], float (&A10)[NS],
+                                                 float (&A11)[NS]) {
+        float t00[NS], t01[NS], t10[NS], t11[NS], d0[NS], d1[NS];
+        load_cell_taps<T, NS>(img, g, c, lane, t00, t01, t10, t11);
+        const int codes = cell_label_codes(tg, g, SC, off, cj, ck, lane, ignore_index);      // -1 / -2: no gradient
+        const float mb = cell_max_bound<NS>(t00, t01, t10, t11, lane, g.C);
+        cell_scaled_taps<NS>(t00, t01, t10, t11, mb, lane, g.C, d0, d1);
+        unsigned slow = 0;
 #pragma unroll 1
-            for (int bi = 0; bi < NB; ++bi) {
-                const int row0 = (bi / BPR) * ROWS, col0 = (bi % BPR) * COLS;
-                float e[PB][NS], ps[PB], dp[PB], tot[PB], dtot[PB];
+        for (int bi = 0; bi < NB; ++bi) {
+            const int row0 = (bi / BPR) * ROWS, col0 = (bi % BPR) * COLS;
+            float e[PB][NS], ps[PB], dp[PB], tot[PB], dtot[PB];
 #pragma unroll
-                for (int i = NPB; i < PB; ++i) { ps[i] = 0.f; dp[i] = 0.f; }
+            for (int i = NPB; i < PB; ++i) { ps[i] = 0.f; dp[i] = 0.f; }
 #pragma unroll
-                for (int r = 0; r < ROWS; ++r) {
-                    const float ly = (float)(row0 + r + 0.5f) / (float)SC;
-                    float L[NS], D[NS];
+            for (int r = 0; r < ROWS; ++r) {
+                const float ly = (float)(row0 + r + 0.5f) / (float)SC;
+                float L[NS], D[NS];
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    L[s] = fmaf(ly, d0[s], t00[s]);
+                    D[s] = fmaf(ly, d1[s], t01[s]) - L[s];
+                }
+#pragma unroll
+                for (int q = 0; q < COLS; ++q) {
+                    const int i = r * COLS + q;
+                    const float lx = (float)(col0 + q + 0.5f) / (float)SC;
+                    const int t = __builtin_amdgcn_readlane(codes, (row0 + r) * SC + col0 + q);
+                    const int tt = t < 0 ? 0 : t;
+                    float sum = 0.f, dsum = 0.f;
 #pragma unroll
                     for (int s = 0; s < NS; ++s) {
-                        L[s] = fmaf(ly, d0[s], t00[s]);
-                        D[s] = fmaf(ly, d1[s], t01[s]) - L[s];
+                        e[i][s] = __builtin_amdgcn_exp2f(fmaf(lx, D[s], L[s]));
+                        sum += e[i][s];
+                        const float G = gP[s] + (lane + 64 * s == tt ? gI[s] : 0.f);
+                        dsum = fmaf(G, e[i][s], dsum);
                     }
-#pragma unroll
-                    for (int q = 0; q < COLS; ++q) {
-                        const int i = r * COLS + q;
-                        const float lx = (float)(col0 + q + 0.5f) / (float)SC;
-                        const int t = __builtin_amdgcn_readlane(codes, (row0 + r) * SC + col0 + q);
-                        const int tt = t < 0 ? 0 : t;
-                        float sum = 0.f, dsum = 0.f;
-#pragma unroll
-                        for (int s = 0; s < NS; ++s) {
-                            e[i][s] = __builtin_amdgcn_exp2f(fmaf(lx, D[s], L[s]));
-                            sum += e[i][s];
-                            const float G = gP[s] + (lane + 64 * s == tt ? gI[s] : 0.f);
-                            dsum = fmaf(G, e[i][s], dsum);
-                        }
-                        ps[i] = sum; dp[i] = dsum;
-                    }
+                    ps[i] = sum; dp[i] = dsum;
                 }
-                wave_reduce8(ps, tot);
-                wave_reduce8(dp, dtot);
+            }
+            wave_reduce8(ps, tot);
+            wave_reduce8(dp, dtot);
 #pragma unroll
-                for (int r = 0; r < ROWS; ++r) {
-                    const float ly = (float)(row0 + r + 0.5f) / (float)SC;
-                    float Rl[NS], Rr[NS];
+            for (int r = 0; r < ROWS; ++r) {
+                const float ly = (float)(row0 + r + 0.5f) / (float)SC;
+                float Rl[NS], Rr[NS];
 #pragma unroll
-                    for (int s = 0; s < NS; ++s) { Rl[s] = 0.f; Rr[s] = 0.f; }
+                for (int s = 0; s < NS; ++s) { Rl[s] = 0.f; Rr[s] = 0.f; }
 #pragma unroll
-                    for (int q = 0; q < COLS; ++q) {
-                        const int i = r * COLS + q;
-                        const float lx = (float)(col0 + q + 0.5f) / (float)SC;
-                        const int t = __builtin_amdgcn_readlane(codes, (row0 + r) * SC + col0 + q);
-                        const int tt = t < 0 ? 0 : t;
-                        const bool under = !(tot[i] > 1e-30f);
-                        if (t >= 0 && under) slow |= 1u;
-                        const float okf = (t >= 0 && !under) ? 1.f : 0.f;
-                        const float inv = okf * __builtin_amdgcn_rcpf(fmaxf(tot[i], 1e-30f));
-                        const float wce = okf != 0.f ? (cw ? cw[tt] : 1.f) * invW : 0.f;   // no CE term, also where invW = 1 / 0 (no valid pixel in the batch)
-                        const float c1 = go * inv, k = wce - dtot[i] * inv, c2 = go * wce;
-#pragma unroll
-                        for (int s = 0; s < NS; ++s) {
-                            const bool own = lane + 64 * s == tt;
-                            const float G = gP[s] + (own ? gI[s] : 0.f);
-                            const float dz = fmaf(c1 * e[i][s], G + k, own ? -c2 : 0.f);      // go * (p (G - <G,p>) + wce (p - [c==t]))
-                            Rl[s] = fmaf(1.f - lx, dz, Rl[s]);
-                            Rr[s] = fmaf(lx, dz, Rr[s]);
-                        }
-                    }
+                for (int q = 0; q < COLS; ++q) {
+                    const int i = r * COLS + q;
+                    const float lx = (float)(col0 + q + 0.5f) / (float)SC;
+                    const int t = __builtin_amdgcn_readlane(codes, (row0 + r) * SC + col0 + q);
+                    const int tt = t < 0 ? 0 : t;
+                    const bool under = !(tot[i] > 1e-30f);
+                    if (t >= 0 && under) slow |= 1u;
+                    const float okf = (t >= 0 && !under) ? 1.f : 0.f;
+                    const float inv = okf * __builtin_amdgcn_rcpf(fmaxf(tot[i], 1e-30f));
+                    const float wce = okf != 0.f ? (cw ? cw[tt] : 1.f) * invW : 0.f;   // no CE term, also where invW = 1 / 0 (no valid pixel in the batch)
+                    const float c1 = go * inv, k = wce - dtot[i] * inv, c2 = go * wce;
 #pragma unroll
                     for (int s = 0; s < NS; ++s) {
-                        A00[s] = fmaf(1.f - ly, Rl[s], A00[s]); A10[s] = fmaf(ly, Rl[s], A10[s]);
-                        A01[s] = fmaf(1.f - ly, Rr[s], A01[s]); A11[s] = fmaf(ly, Rr[s], A11[s]);
+                        const bool own = lane + 64 * s == tt;
+                        const float G = gP[s] + (own ? gI[s] : 0.f);
+                        const float dz = fmaf(c1 * e[i][s], G + k, own ? -c2 : 0.f);      // go * (p (G - <G,p>) + wce (p - [c==t]))
+                        Rl[s] = fmaf(1.f - lx, dz, Rl[s]);
+                        Rr[s] = fmaf(lx, dz, Rr[s]);
                     }
                 }
-            }
-            if (slow && lane == 0) atomicOr(retry, 1);
-            // the taps live in the exp2 domain: d zq / d logit = log2(e) is NOT wanted -- dz above is already d loss / d logit
-            const int ly0 = c.y0 - ty0, ly1 = c.y1 - ty0, lx0 = c.x0 - tx0, lx1 = c.x1 - tx0;
-            const bool vy0 = ly0 >= 0 && ly0 < LS_TILE, vy1 = ly1 >= 0 && ly1 < LS_TILE;
-            const bool vx0 = lx0 >= 0 && lx0 < LS_TILE, vx1 = lx1 >= 0 && lx1 < LS_TILE;
 #pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const int cc = lane + 64 * s;
-                if (vy0 && vx0) accum[ly0 * LS_TILE + lx0][cc] += A00[s];
-                if (vy0 && vx1) accum[ly0 * LS_TILE + lx1][cc] += A01[s];
-                if (vy1 && vx0) accum[ly1 * LS_TILE + lx0][cc] += A10[s];
-                if (vy1 && vx1) accum[ly1 * LS_TILE + lx1][cc] += A11[s];
+                for (int s = 0; s < NS; ++s) {
+                    A00[s] = fmaf(1.f - ly, Rl[s], A00[s]); A10[s] = fmaf(ly, Rl[s], A10[s]);
+                    A01[s] = fmaf(1.f - ly, Rr[s], A01[s]); A11[s] = fmaf(ly, Rr[s], A11[s]);
+                }
             }
         }
-        __syncthreads();
-    }
-    for (int tap = wave; tap < LS_TILE * LS_TILE; tap += 4) {
-        const int y = ty0 + tap / LS_TILE, x = tx0 + tap % LS_TILE;
-        if (y >= g.h || x >= g.w) continue;
-        T* drow = dlow + (((int64_t)b * g.h + y) * g.w + x) * ldd;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int cc = lane + 64 * s;
-            if (cc < ldd) stf<T>(drow + cc, cc < g.C ? accum[tap][cc] : 0.f);
-        }
-    }
+        if (slow && lane == 0) atomicOr(retry, 1);
+        // the taps live in the exp2 domain: d zq / d logit = log2(e) is NOT wanted -- dz above is already d loss / d logit
+        return true;
+    });
 }
 
 // ---- MFMA form of the cell kernels (SC == 4) ---------------------------------------------------------------------------
@@ -1117,17 +932,14 @@ __global__ void __launch_bounds__(LS_THREADS) ce_dice_bwd_kernel(const T* __rest
                                                                   const float* __restrict__ stats, const float* __restrict__ grad_out,
                                                                   T* __restrict__ dfull, int64_t ldg) {
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.y;
     float gI[NS], gP[NS];
     dice_coefs<NS>(stats, b, g.B, g.C, dice, lane, gI, gP);
     const float go = grad_out ? grad_out[0] : 1.f;
     const float invW = 1.f / stats[(int64_t)g.B * (3 * g.C + 4) + 1];
     const int64_t npix = (int64_t)g.H * g.W;
-    const int64_t nw = (int64_t)gridDim.x * 4;
-    const int64_t per = (npix + nw - 1) / nw;
-    const int64_t wid = (int64_t)blockIdx.x * 4 + wave;
-    const int64_t p0 = wid * per, p1 = p0 + per < npix ? p0 + per : npix;
+    int64_t p0, p1;
+    wave_pixel_range(npix, p0, p1);
     const T* img = logits + (int64_t)b * g.h * g.w * g.ldl;
     const int64_t* tg = target + (int64_t)b * npix;
     T* dimg = dfull + (int64_t)b * npix * ldg;
@@ -1171,8 +983,6 @@ extern "C" int segf_debug_wave_reduce16(const float* in, float* out, void* strea
 extern "C" int64_t segf_ce_dice_stats_floats(int B, int C) {
     return (int64_t)B * (3 * C + 4) + 4 + (int64_t)LS_NBLK * B * (3 * C + 4) + 4;      // + retry flags
 }
-
-#define LS_NS_DISPATCH(ns, CALL) do { if ((ns) == 1) { CALL(1); } else if ((ns) == 2) { CALL(2); } else { CALL(3); } } while (0)
 
 __global__ void zero_words_kernel(uint32_t* __restrict__ p, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = 0u;
@@ -1353,15 +1163,6 @@ __device__ __forceinline__ int wave_argmax(const float (&z)[NS], int lane, int C
     const int bi = (int)best;
     return bi < C ? bi : 0;        // all-NaN row
 }
-__device__ __forceinline__ void confmat_count(int64_t t, int pred, int C, int64_t ignore_label, unsigned long long* mat,
-                                              unsigned long long* hist, int* flag) {
-    const bool in_mat = t >= 0 && t < C;
-    if (in_mat) atomicAdd(mat + t * C + pred, 1ull);
-    if (t != ignore_label) {
-        if (in_mat) atomicAdd(hist + t * C + pred, 1ull);
-        else atomicOr(flag, 1);    // label >= n that is not ignore_label: the reference's bincount shape check fails
-    }
-}
 
 template <typename T, int NS>
 __global__ void __launch_bounds__(LS_THREADS) argmax_confmat_cells_kernel(const T* __restrict__ logits, LossGeom g, int sc,
@@ -1414,7 +1215,7 @@ __global__ void __launch_bounds__(LS_THREADS) argmax_confmat_cells_kernel(const 
             const int a = lane / sc, bb = lane - a * sc;
             const int Y = sc * c.cj + off + a, X = sc * c.ck + off + bb;
             if (pred_out) pred_out[(int64_t)b * npix + (int64_t)Y * g.W + X] = preds;
-            if (codes != -3) confmat_count(raw, preds, g.C, ignore_label, mat, hist, flag);
+            if (codes != -3) eval_count(raw, preds, g.C, ignore_label, mat, hist, flag);
         }
     }
 }
@@ -1426,13 +1227,10 @@ __global__ void __launch_bounds__(LS_THREADS) argmax_confmat_kernel(const T* __r
                                                                      unsigned long long* __restrict__ hist, int* __restrict__ flag,
                                                                      int64_t* __restrict__ pred_out) {
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.y;
     const int64_t npix = (int64_t)g.H * g.W;
-    const int64_t nw = (int64_t)gridDim.x * 4;
-    const int64_t per = (npix + nw - 1) / nw;
-    const int64_t wid = (int64_t)blockIdx.x * 4 + wave;
-    const int64_t p0 = wid * per, p1 = p0 + per < npix ? p0 + per : npix;
+    int64_t p0, p1;
+    wave_pixel_range(npix, p0, p1);
     const T* img = logits + (int64_t)b * g.h * g.w * g.ldl;
     const int64_t* tg = target + (int64_t)b * npix;
     for (int64_t p = p0; p < p1; ++p) {
@@ -1444,7 +1242,7 @@ __global__ void __launch_bounds__(LS_THREADS) argmax_confmat_kernel(const T* __r
         const int best = wave_argmax<NS>(z, lane, g.C);
         if (lane == 0) {
             if (pred_out) pred_out[(int64_t)b * npix + p] = best;
-            confmat_count(t, best, g.C, ignore_label, mat, hist, flag);
+            eval_count(t, best, g.C, ignore_label, mat, hist, flag);
         }
     }
 }

@@ -13,8 +13,9 @@
 // Ties at kappa: torch.topk keeps arbitrary members; here every pixel with ce == kappa receives the share
 // (n_min - n_gt) / (n_eq * n_min) -- the loss equals the reference's, the gradient is a deterministic member of its possible ones.
 // Backward: coef(pixel) * w[t] * (softmax - onehot) scattered through the transposed resize onto the low-res taps with the tile /
-// parity-colour structure of ce_dice_bwd_cells_kernel (loss.hip); the side of the decision value is read from the SAVED map, so
+// parity-colour structure of tile_cells_walk (loss_geom.h); the side of the decision value is read from the SAVED map, so
 // forward and backward agree on every pixel.  Non-power-of-two ratios stage the full-resolution gradient and use segf_bilinear_bwd.
+// The class-row helpers (tap loads, wave softmax, cell taps and bound) are those of loss_geom.h; the backward keeps its own copy of the walk.
 #include "loss_geom.h"
 
 namespace {
@@ -29,24 +30,9 @@ struct PixelParams { int mode; float p0, p1; int size_average; };     // OHEM: p
 
 __device__ __forceinline__ int ld_state(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-inline int px_pow2_scale(int h, int w, int H, int W) {
-    if (h <= 0 || w <= 0 || H % h || W % w) return 0;
-    const int sc = H / h;
-    if (W / w != sc || (sc & (sc - 1)) || sc > 8) return 0;
-    return sc;
-}
-
-template <typename T, int NS>
-__device__ __forceinline__ void px_load_tap(const T* __restrict__ p, int lane, int C, float (&t)[NS]) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const int c = lane + 64 * s;
-        const float v = ldf<T>(p + (c < C ? c : C - 1));
-        t[s] = c < C ? v : 0.f;
-    }
-}
-
-// upsampled logits of one pixel at ATen's source index and tap weights (any ratio); invalid class slots get -inf
+// upsampled logits of one pixel at ATen's source index and tap weights (any ratio); invalid class slots get -inf.  pixel_logits
+// (loss_geom.h) without its same-size branch, which no caller here can reach and which costs pixel_loss_fwd_kernel<T, 3> a wave of
+// occupancy (SGPRs)
 template <typename T, int NS>
 __device__ __forceinline__ void px_pixel_logits(const T* __restrict__ img, const LossGeom& g, int Y, int X, int lane, float (&z)[NS]) {
     int y0, y1, x0, x1; float ly, lx;
@@ -62,47 +48,6 @@ __device__ __forceinline__ void px_pixel_logits(const T* __restrict__ img, const
         const float a = ldf<T>(p00 + ci), b = ldf<T>(p01 + ci), cc = ldf<T>(p10 + ci), d = ldf<T>(p11 + ci);
         z[s] = c < g.C ? (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * cc + lx * d) : -INFINITY;
     }
-}
-
-// softmax over the wave with the exact maximum mx: p[s]; returns log(sum exp(z - mx)) (wave-uniform).  The caller forms
-// ce = log(sum) - (z_t - mx): at a confident pixel (z_t == mx, sum = 1 + eps) nothing of the size of the logits enters, so a ce of
-// 1e-5 keeps an absolute error of the roundings of the sum (~1e-7) instead of that of mx + log(sum) (half an ulp of the logit)
-template <int NS>
-__device__ __forceinline__ float px_softmax(const float (&z)[NS], float (&p)[NS], float& mx_out) {
-    float mx = z[0];
-#pragma unroll
-    for (int s = 1; s < NS; ++s) mx = fmaxf(mx, z[s]);
-    mx = wave_max_all(mx);
-    float sum = 0.f;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) { p[s] = __expf(z[s] - mx); sum += p[s]; }
-    sum = wave_sum_all(sum);
-    const float inv = 1.f / sum;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) p[s] *= inv;
-    mx_out = mx;
-    return __logf(sum);
-}
-// z_t for a wave-uniform label t: class c lives in lane c % 64, slot c / 64
-template <int NS>
-__device__ __forceinline__ float px_label_logit(const float (&z)[NS], int t) {
-    float v = z[0];
-#pragma unroll
-    for (int s = 1; s < NS; ++s) v = (t >> 6) == s ? z[s] : v;
-    return readlane_f(v, t & 63);
-}
-// softmax probabilities with a wave-uniform upper bound mb of max(z) in place of the exact maximum (a cell's pixels are convex
-// combinations of its four taps: one reduction per cell instead of one per pixel); exact-maximum path if the sum underflows
-template <int NS>
-__device__ __forceinline__ void px_softmax_bounded(const float (&z)[NS], float mb, float (&p)[NS]) {
-    float sum = 0.f;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) { p[s] = __expf(z[s] - mb); sum += p[s]; }
-    sum = wave_sum_all(sum);
-    if (!(sum > 1e-30f)) { float mx; px_softmax<NS>(z, p, mx); return; }
-    const float inv = 1.f / sum;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) p[s] *= inv;
 }
 
 // focal: f = alpha (1 - pt)^gamma ce; its derivative with respect to ce, without alpha: (1 - pt)^gamma + gamma (1 - pt)^(gamma-1) pt ce
@@ -170,15 +115,18 @@ __global__ void __launch_bounds__(LS_THREADS) pixel_loss_fwd_cells_kernel(const 
     float* cm = ce_map + (int64_t)b * g.H * g.W;
     PxAcc acc{0, 0, 0, 0.f};
     for (int cell = blockIdx.x * 4 + wave; cell < ncell; cell += gridDim.x * 4) {
+        // clamps and loads written out, not make_cell / load_cell_taps: with them the ratio-8 forward was 0.7 % slower, outside the
+        // parent-to-parent spread (profiles/loss_rows.md)
         const int cj = cell / ncx - halo, ck = cell % ncx - halo;
         const int y0 = cj < 0 ? 0 : cj, y1 = cj + halo > g.h - 1 ? g.h - 1 : cj + halo;
         const int x0 = ck < 0 ? 0 : ck, x1 = ck + halo > g.w - 1 ? g.w - 1 : ck + halo;
         float t00[NS], t01[NS], t10[NS], t11[NS];
-        px_load_tap<T, NS>(img + ((int64_t)y0 * g.w + x0) * g.ldl, lane, g.C, t00);
-        px_load_tap<T, NS>(img + ((int64_t)y0 * g.w + x1) * g.ldl, lane, g.C, t01);
-        px_load_tap<T, NS>(img + ((int64_t)y1 * g.w + x0) * g.ldl, lane, g.C, t10);
-        px_load_tap<T, NS>(img + ((int64_t)y1 * g.w + x1) * g.ldl, lane, g.C, t11);
+        load_tap<T, NS>(img + ((int64_t)y0 * g.w + x0) * g.ldl, lane, g.C, t00);
+        load_tap<T, NS>(img + ((int64_t)y0 * g.w + x1) * g.ldl, lane, g.C, t01);
+        load_tap<T, NS>(img + ((int64_t)y1 * g.w + x0) * g.ldl, lane, g.C, t10);
+        load_tap<T, NS>(img + ((int64_t)y1 * g.w + x1) * g.ldl, lane, g.C, t11);
         // this lane's pixel of the cell (lane = a * sc + bb): code = class, -1 ignored, -2 out of range, -3 outside the image
+        // (not cell_label_codes: an ignored pixel inside the image still gets its +0.0 written, so "outside" needs a code of its own)
         int code = -3, myY = 0, myX = 0;
         if (lane < sc * sc) {
             const int a = lane / sc;
@@ -207,7 +155,7 @@ __global__ void __launch_bounds__(LS_THREADS) pixel_loss_fwd_cells_kernel(const 
 #pragma unroll
                 for (int s = 0; s < NS; ++s) z[s] = (lane + 64 * s) < g.C ? (1.f - lx) * L[s] + lx * R[s] : -INFINITY;
                 float mx;
-                const float lsum = px_softmax<NS>(z, pr, mx);
+                const float lsum = wave_softmax<NS>(z, pr, mx);
                 const float ce = fmaxf((cw ? cw[t] : 1.f) * (lsum - (px_label_logit<NS>(z, t) - mx)), 0.f);
                 if (lane == a * sc + bb) myce = ce;
             }
@@ -230,13 +178,10 @@ __global__ void __launch_bounds__(LS_THREADS) pixel_loss_fwd_kernel(const T* __r
                                                                      float* __restrict__ ce_map, int* __restrict__ state,
                                                                      float* __restrict__ partial) {
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.y;
     const int64_t npix = (int64_t)g.H * g.W;
-    const int64_t nw = (int64_t)gridDim.x * 4;
-    const int64_t per = (npix + nw - 1) / nw;
-    const int64_t wid = (int64_t)blockIdx.x * 4 + wave;
-    const int64_t p0 = wid * per, p1 = p0 + per < npix ? p0 + per : npix;
+    int64_t p0, p1;
+    wave_pixel_range(npix, p0, p1);
     const T* img = logits + (int64_t)b * g.h * g.w * g.ldl;
     const int64_t* tg = target + (int64_t)b * npix;
     float* cm = ce_map + (int64_t)b * npix;
@@ -250,7 +195,7 @@ __global__ void __launch_bounds__(LS_THREADS) pixel_loss_fwd_kernel(const T* __r
             float z[NS], pr[NS];
             px_pixel_logits<T, NS>(img, g, Y, X, lane, z);
             float mx;
-            const float lsum = px_softmax<NS>(z, pr, mx);
+            const float lsum = wave_softmax<NS>(z, pr, mx);
             ce = fmaxf((cw ? cw[t] : 1.f) * (lsum - (px_label_logit<NS>(z, (int)t) - mx)), 0.f);
         }
         if (lane == 0) {
@@ -392,6 +337,9 @@ __device__ __forceinline__ float px_coef(const PxCoef& c, float ce) {
 
 // Workgroup = LS_TILE x LS_TILE low-res taps of one image; it evaluates the (LS_TILE+1)^2 cells that touch them (halo cells are
 // recomputed by the neighbouring workgroup), four parity colours so that no two cells in flight share a tap, plain stores.
+// Its own copy of the walk that tile_cells_walk (loss_geom.h) holds: on the shared walk the <float, 3> instantiation changed output
+// bits, and with make_cell / load_cell_taps / cell_max_bound in place of the clamps, loads and bound written out below the kernel
+// was 2.4 % slower (profiles/loss_rows.md).  A change to the scatter or the store below belongs in tile_cells_walk too.
 template <typename T, int NS>
 __global__ void __launch_bounds__(LS_THREADS) pixel_loss_bwd_cells_kernel(const T* __restrict__ logits, LossGeom g, int sc,
                                                                            const int64_t* __restrict__ target, int64_t ignore_index,
@@ -439,10 +387,10 @@ __global__ void __launch_bounds__(LS_THREADS) pixel_loss_bwd_cells_kernel(const 
             const int y0 = cj < 0 ? 0 : cj, y1 = cj + halo > g.h - 1 ? g.h - 1 : cj + halo;
             const int x0 = ck < 0 ? 0 : ck, x1 = ck + halo > g.w - 1 ? g.w - 1 : ck + halo;
             float t00[NS], t01[NS], t10[NS], t11[NS], A00[NS], A01[NS], A10[NS], A11[NS];
-            px_load_tap<T, NS>(img + ((int64_t)y0 * g.w + x0) * g.ldl, lane, g.C, t00);
-            px_load_tap<T, NS>(img + ((int64_t)y0 * g.w + x1) * g.ldl, lane, g.C, t01);
-            px_load_tap<T, NS>(img + ((int64_t)y1 * g.w + x0) * g.ldl, lane, g.C, t10);
-            px_load_tap<T, NS>(img + ((int64_t)y1 * g.w + x1) * g.ldl, lane, g.C, t11);
+            load_tap<T, NS>(img + ((int64_t)y0 * g.w + x0) * g.ldl, lane, g.C, t00);
+            load_tap<T, NS>(img + ((int64_t)y0 * g.w + x1) * g.ldl, lane, g.C, t01);
+            load_tap<T, NS>(img + ((int64_t)y1 * g.w + x0) * g.ldl, lane, g.C, t10);
+            load_tap<T, NS>(img + ((int64_t)y1 * g.w + x1) * g.ldl, lane, g.C, t11);
             float mb = -INFINITY;
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
@@ -463,10 +411,10 @@ __global__ void __launch_bounds__(LS_THREADS) pixel_loss_bwd_cells_kernel(const 
                     const float cf = readlane_f(coef, a * sc + bb);
                     if (t < 0 || cf == 0.f) continue;
                     const float lx = (bb + 0.5f) * inv_sc * fhalo;
-                    float z[NS], pr[NS];
+                    float z[NS], pr[NS], shift;
 #pragma unroll
                     for (int s = 0; s < NS; ++s) z[s] = (lane + 64 * s) < g.C ? (1.f - lx) * L[s] + lx * R[s] : -INFINITY;
-                    px_softmax_bounded<NS>(z, mb, pr);
+                    wave_softmax_bounded<NS>(z, mb, pr, shift);
                     const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
 #pragma unroll
                     for (int s = 0; s < NS; ++s) {
@@ -511,14 +459,11 @@ __global__ void __launch_bounds__(LS_THREADS) pixel_loss_bwd_kernel(const T* __r
                                                                      const float* __restrict__ grad_out, T* __restrict__ dfull,
                                                                      int64_t ldg) {
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.y;
     const PxCoef pc = px_coef_setup(state, pp, grad_out);
     const int64_t npix = (int64_t)g.H * g.W;
-    const int64_t nw = (int64_t)gridDim.x * 4;
-    const int64_t per = (npix + nw - 1) / nw;
-    const int64_t wid = (int64_t)blockIdx.x * 4 + wave;
-    const int64_t p0 = wid * per, p1 = p0 + per < npix ? p0 + per : npix;
+    int64_t p0, p1;
+    wave_pixel_range(npix, p0, p1);
     const T* img = logits + (int64_t)b * g.h * g.w * g.ldl;
     const int64_t* tg = target + (int64_t)b * npix;
     const float* cm = ce_map + (int64_t)b * npix;
@@ -536,7 +481,7 @@ __global__ void __launch_bounds__(LS_THREADS) pixel_loss_bwd_kernel(const T* __r
                 float z[NS], pr[NS];
                 px_pixel_logits<T, NS>(img, g, Y, X, lane, z);
                 float mx;
-                px_softmax<NS>(z, pr, mx);
+                wave_softmax<NS>(z, pr, mx);
 #pragma unroll
                 for (int s = 0; s < NS; ++s) dz[s] = cf * (pr[s] - (lane + 64 * s == (int)t ? 1.f : 0.f));
             }
@@ -553,8 +498,6 @@ __global__ void pixel_loss_zero_words_kernel(uint32_t* __restrict__ p, int64_t n
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = 0u;
 }
 
-#define PX_NS_DISPATCH(ns, CALL) do { if ((ns) == 1) { CALL(1); } else if ((ns) == 2) { CALL(2); } else { CALL(3); } } while (0)
-
 template <typename T>
 void px_fwd_launch(int ns, int sc, dim3 grid, hipStream_t st, const T* logits, LossGeom g, const int64_t* target, int64_t ignore_index,
                    const float* cw, PixelParams pp, float* ce_map, int* state, float* partial) {
@@ -565,7 +508,7 @@ void px_fwd_launch(int ns, int sc, dim3 grid, hipStream_t st, const T* logits, L
         else hipLaunchKernelGGL((pixel_loss_fwd_kernel<T, NS>), grid, dim3(LS_THREADS), 0, st, logits, g, target, ignore_index,  \
                                 cw, pp, ce_map, state, partial);                                                                 \
     } while (0)
-    PX_NS_DISPATCH(ns, CALL);
+    LS_NS_DISPATCH(ns, CALL);
 #undef CALL
 }
 template <typename T>
@@ -578,7 +521,7 @@ void px_bwd_launch(int ns, int sc, dim3 grid, hipStream_t st, const T* logits, L
         else hipLaunchKernelGGL((pixel_loss_bwd_kernel<T, NS>), grid, dim3(LS_THREADS), 0, st, logits, g, target, ignore_index,  \
                                 cw, pp, ce_map, state, grad_out, dst, ld);                                                       \
     } while (0)
-    PX_NS_DISPATCH(ns, CALL);
+    LS_NS_DISPATCH(ns, CALL);
 #undef CALL
 }
 
@@ -605,7 +548,7 @@ extern "C" int64_t segf_pixel_loss_state_words(int B) {
 }
 
 extern "C" int64_t segf_pixel_loss_bwd_ws(int dt, int B, int C, int h, int w, int H, int W) {
-    if (!segf_pixel_loss_supported(dt, PX_MODE_OHEM, B, C, h, w, H, W) || px_pow2_scale(h, w, H, W)) return 0;
+    if (!segf_pixel_loss_supported(dt, PX_MODE_OHEM, B, C, h, w, H, W) || pow2_scale(h, w, H, W)) return 0;
     const int64_t ldg = (C + 7) / 8 * 8;
     const int64_t bytes = (int64_t)B * H * W * ldg * (dt == SEGF_BF16 ? 2 : 4);
     return (bytes + 3) / 4;
@@ -620,7 +563,7 @@ extern "C" int segf_pixel_loss_fwd(int dt, int mode, int B, int C, int h, int w,
     hipStream_t st = (hipStream_t)stream;
     LossGeom g{B, C, h, w, H, W, ldl};
     const int ns = (C + 63) / 64;
-    const int sc = px_pow2_scale(h, w, H, W);
+    const int sc = pow2_scale(h, w, H, W);
     const int64_t npix = (int64_t)B * H * W;
     float* partial = reinterpret_cast<float*>(state) + PXS_HEAD + PXS_HIST;
     float* rpartial = partial + (int64_t)LS_NBLK * B;
@@ -658,7 +601,7 @@ extern "C" int segf_pixel_loss_bwd(int dt, int mode, int B, int C, int h, int w,
     hipStream_t st = (hipStream_t)stream;
     LossGeom g{B, C, h, w, H, W, ldl};
     const int ns = (C + 63) / 64;
-    const int sc = px_pow2_scale(h, w, H, W);
+    const int sc = pow2_scale(h, w, H, W);
     if (sc) {
         const dim3 grid(((h + LS_TILE - 1) / LS_TILE) * ((w + LS_TILE - 1) / LS_TILE), B);
         SEGF_DISPATCH_DT(dt, T, { px_bwd_launch<T>(ns, sc, grid, st, (const T*)logits, g, target, ignore_index, class_weight, pp, ce_map, state, grad_out, (T*)dlogits, ldd); })

@@ -77,7 +77,7 @@ def make_target(B, H, W, C, ignore_label=255, bad_label=None, seed=1):
 
 
 def counts(target, pred, C, ignore_label):
-    """(mat, hist) int64 [C, C] of confmat_count: torch bincount of (target, pred) over all pixels."""
+    """(mat, hist) int64 [C, C] of eval_count (csrc/eval_rows.h): torch bincount of (target, pred) over all pixels."""
     t, p = target.flatten(), pred.flatten()
     in_mat = (t >= 0) & (t < C)
     mat = torch.bincount(t[in_mat] * C + p[in_mat], minlength=C * C).view(C, C)

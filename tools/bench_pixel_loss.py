@@ -1,6 +1,9 @@
 """Time the per-pixel loss kernels (segf_pixel_loss_fwd / _bwd, csrc/loss_pixel.hip) at the cfg2 head shape -- 150 classes, 128 x 128
 -> 512 x 512, bf16 rows of 152 columns, batch 32 -- beside the existing CE + Dice pair with dice = 0 at the same shape in the same process.
-Usage: python tools/bench_pixel_loss.py [--out profiles/pixel_loss.md] [--iters 50] [--batch 32] [--only ohem_thresh|ohem_topk|focal|ce_dice]
+Usage: python tools/bench_pixel_loss.py [--out profiles/pixel_loss.md] [--iters 50] [--batch 32] [--low 128]
+                                        [--only ohem_thresh|ohem_topk|focal|ce_dice]
+--low: edge of the low-resolution map, 512 / low in {2, 4, 8}.  At 128 (ratio 4, the default) the CE + Dice row runs the band kernels; at 256
+and 64 it runs ce_dice_fwd_cells16_kernel / ce_dice_bwd_cells8_kernel, and the pixel rows their cell kernels at that ratio.
 
 Rows: OHEM in the threshold branch (random logits: most pixels are hard, the eight selection kernels and the two top-k reductions are
 launched and return at once), OHEM in the top-k branch (one class per image raised by 9: few pixels are hard, the radix select and the
@@ -32,10 +35,10 @@ def timed(fn, iters):
     return e0.elapsed_time(e1) / iters * 1e3          # microseconds
 
 
-def make_inputs(B, confident):
+def make_inputs(B, low, confident):
     g = torch.Generator(device='cuda').manual_seed(1 if confident else 0)
-    wide = torch.zeros(B * LOW * LOW, LD, dtype=torch.bfloat16, device='cuda')
-    lo = torch.randn(B, LOW, LOW, C, generator=g, device='cuda')
+    wide = torch.zeros(B * low * low, LD, dtype=torch.bfloat16, device='cuda')
+    lo = torch.randn(B, low, low, C, generator=g, device='cuda')
     t = torch.randint(0, C, (B, FULL, FULL), generator=g, device='cuda')
     if confident:
         kb = torch.randint(0, C, (B,), generator=g, device='cuda')
@@ -54,16 +57,17 @@ def main():
     ap.add_argument('--iters', type=int, default=50)
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--only', default='')
+    ap.add_argument('--low', type=int, default=LOW, choices=(64, 128, 256))
     a = ap.parse_args()
-    B = a.batch
-    geom = (B, C, LOW, LOW, FULL, FULL)
+    B, low = a.batch, a.low
+    geom = (B, C, low, low, FULL, FULL)
     go = torch.ones(1, device='cuda')
     rows = []
 
     def pixel(name, confident, mode, p0, p1):
         if a.only and a.only != name:
             return
-        x, t = make_inputs(B, confident)
+        x, t = make_inputs(B, low, confident)
         args = (x, *geom, t, IGNORE, None, mode, p0, p1, 1)
         loss, ce_map, state = hip.pixel_loss_fwd(*args)
         info = state[:8].cpu().tolist()
@@ -77,7 +81,7 @@ def main():
     pixel('ohem_topk', True, hip.PIXEL_OHEM, THETA, 0.0)
     pixel('focal', False, hip.PIXEL_FOCAL, 0.25, 2.0)
     if not a.only or a.only == 'ce_dice':
-        x, t = make_inputs(B, False)
+        x, t = make_inputs(B, low, False)
         loss, stats, lse = hip.ce_dice_fwd(x, *geom, t, IGNORE, None, 0, want_lse=True)
         t_f = timed(lambda: hip.ce_dice_fwd(x, *geom, t, IGNORE, None, 0, want_lse=True), a.iters)
         t_b = timed(lambda: hip.ce_dice_bwd(x, *geom, t, IGNORE, None, 0, stats, go, lse=lse), a.iters)
@@ -91,7 +95,7 @@ def main():
     print(text)
     if a.out:
         with open(a.out, 'w') as fh:
-            fh.write(f'# Per-pixel losses (csrc/loss_pixel.hip) at C = {C}, {LOW}^2 -> {FULL}^2, bf16, batch {B}, MI355X: '
+            fh.write(f'# Per-pixel losses (csrc/loss_pixel.hip) at C = {C}, {low}^2 -> {FULL}^2, bf16, batch {B}, MI355X: '
                      f'tools/bench_pixel_loss.py\n\n' + text)
 
 
