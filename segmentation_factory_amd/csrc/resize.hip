@@ -87,6 +87,9 @@ __global__ void __launch_bounds__(256) upsample_add_kernel(const T* __restrict__
 // strip of four output pixels (X = 4k .. 4k+3) of one row: their horizontal taps are the static sets {2k-1..2k+2},
 // {k-1..k+1} and {(k-1)>>1, +1} with literal weights, the vertical blend is done once per tap column, and the strip needs
 // 22 loads for 4 stores.  Clamped border taps reproduce bilinear_src exactly (both taps of a clamped pair coincide).
+// The strip updates are explicit fma chains: written as `acc += a * u + b * v`, with the contraction (and the sharing of a product
+// between neighbouring pixels) left to the compiler, the <T, true> instantiation stored fp32 results that differed in the last bit
+// from those of <T, false> (tests/test_resize_float64.py::test_upsample_add_stats), i.e. segf_upsample_add_stats from segf_upsample_add.
 template <typename T, int NT>
 __device__ __forceinline__ void load_vblend(const T* __restrict__ sb, const UpSrc& s, int y0, int y1, float ly, int xfirst,
                                             float (&tv)[NT][8]) {
@@ -139,10 +142,10 @@ __global__ void __launch_bounds__(256) upsample_add_248_kernel(const T* __restri
             load_vblend<T, 4>(reinterpret_cast<const T*>(s0.p) + b * s0.h * s0.w * s0.ld + c0, s0, y0, y1, ly, 2 * k - 1, tv);
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
-                acc[0][c] += 0.25f * tv[0][c] + 0.75f * tv[1][c];
-                acc[1][c] += 0.75f * tv[1][c] + 0.25f * tv[2][c];
-                acc[2][c] += 0.25f * tv[1][c] + 0.75f * tv[2][c];
-                acc[3][c] += 0.75f * tv[2][c] + 0.25f * tv[3][c];
+                acc[0][c] = fmaf(0.25f, tv[0][c], fmaf(0.75f, tv[1][c], acc[0][c]));
+                acc[1][c] = fmaf(0.25f, tv[2][c], fmaf(0.75f, tv[1][c], acc[1][c]));
+                acc[2][c] = fmaf(0.25f, tv[1][c], fmaf(0.75f, tv[2][c], acc[2][c]));
+                acc[3][c] = fmaf(0.25f, tv[3][c], fmaf(0.75f, tv[2][c], acc[3][c]));
             }
         }
         {   // 1/4
@@ -151,10 +154,10 @@ __global__ void __launch_bounds__(256) upsample_add_248_kernel(const T* __restri
             load_vblend<T, 3>(reinterpret_cast<const T*>(s1.p) + b * s1.h * s1.w * s1.ld + c0, s1, y0, y1, ly, k - 1, tv);
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
-                acc[0][c] += 0.375f * tv[0][c] + 0.625f * tv[1][c];
-                acc[1][c] += 0.125f * tv[0][c] + 0.875f * tv[1][c];
-                acc[2][c] += 0.875f * tv[1][c] + 0.125f * tv[2][c];
-                acc[3][c] += 0.625f * tv[1][c] + 0.375f * tv[2][c];
+                acc[0][c] = fmaf(0.375f, tv[0][c], fmaf(0.625f, tv[1][c], acc[0][c]));
+                acc[1][c] = fmaf(0.125f, tv[0][c], fmaf(0.875f, tv[1][c], acc[1][c]));
+                acc[2][c] = fmaf(0.125f, tv[2][c], fmaf(0.875f, tv[1][c], acc[2][c]));
+                acc[3][c] = fmaf(0.375f, tv[2][c], fmaf(0.625f, tv[1][c], acc[3][c]));
             }
         }
         {   // 1/8: strip k lies inside one source cell

@@ -23,8 +23,10 @@ of the three weight-gradient plans and the walk kernel's own grid-stride loop.
 
 Not covered by this module: kernels with a division or a transcendental.  Of those the norms and the column reductions (LayerNorm,
 BatchNorm, GRN, colsum) are checked against float64 in tests/test_norm_float64.py, and GELU and its derivative inside the depthwise
-kernels in tests/test_dwconv_float64.py; softmax-CE and fp8 quantisation keep their tolerance tests, as do the bilinear backward / fused forms (bilinear_bwd, bilinear_bwd_248, upsample_add, fuse_map_248) and the pure data movers
-(im2col, col2im, permute021, nearest_up, cast2d), for which tests/exact_inputs.py has no reference yet.
+kernels in tests/test_dwconv_float64.py; softmax-CE and fp8 quantisation keep their tolerance tests.  The bilinear backward and fused forms (bilinear_bwd and its
+integer-ratio kernels, bilinear_bwd_248 on the VALU and on the matrix pipe, upsample_add (+ statistics), fuse_map_248), adaptive_avgpool
+and nearest_up are checked bit for bit on lattice inputs, and per element against float64 on other inputs, in tests/test_resize_float64.py
+(references: tests/resize_refs.py).  The pure data movers im2col, col2im, permute021 and cast2d keep their tolerance tests: no reference yet.
 """
 import ctypes as C
 import json

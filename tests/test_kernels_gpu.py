@@ -9,7 +9,12 @@ tests/test_norm_float64.py.  The depthwise convolutions (for a 3 x 3 tap sum a d
 passes here too) have their tight checks in tests/test_dwconv_float64.py -- every form (strip, walk, one-launch, Mix-FFN, deferred
 finalize, 7 x 7) against float64 under per-element derived bounds at the shapes where the dispatch changes -- and, on lattice inputs with
 zero tolerance, in tests/test_exact_kernels.py; test_dwconv3x3_gelu, test_dwconv7x7 and the form-against-form tests below stay as the
-coarse bar.  Not covered anywhere: the block caps of the depthwise weight-gradient plans and the walk kernel's own grid-stride loop."""
+coarse bar.  The resize family (a dropped corner tap of the 1/8 level weighs 1/256, a lost clamp share 1/16 of one source: both pass
+`_close`) -- bilinear_fwd / bilinear_bwd, the integer-ratio kernels, bilinear_bwd_248 in both forms, upsample_add (+ statistics),
+fuse_map_248, bilinear_to_nchw_f32, adaptive_avgpool, nearest_up -- has its per-element float64 and bit-exact lattice checks in
+tests/test_resize_float64.py; test_bilinear, test_upsample_add_*, test_fuse_map_248_one_pass, test_bilinear_bwd_248_* and
+test_nearest_up_* below stay as the coarse bar.
+Not covered anywhere: the block caps of the depthwise weight-gradient plans and the walk kernel's own grid-stride loop."""
 import math
 import os
 
