@@ -767,6 +767,56 @@ int segf_slide_argmax_confmat(int dt, int B, int C, int H, int W, int ch, int cw
                               int64_t* mat, int64_t* hist, int32_t* flag,
                               int64_t* pred_out /*nullable*/, float* mean_out /*nullable*/, int64_t ldm, void* stream);
 
+/* ---- multi-scale + flip SLIDING-WINDOW evaluation: the two entries above composed in one kernel (csrc/eval_msf_slide.hip).
+ * mmseg's aug_test with mode='slide', the protocol behind SegFormer's multi-scale Cityscapes figures: at every scale, straight and
+ * horizontally mirrored, the model runs on overlapping crops of the SCALED image; the logits of overlapping crops are averaged, the
+ * mean map is resized to the label size (H, W) and softmaxed, the probability maps of all (scale, flip) pairs are summed and the arg
+ * max of the sum is scored.  No full-resolution map, at the label size or at a scaled size, exists here.
+ * n <= SEGF_MSF_MAX_MAPS window sets of one dtype dt.  Set k belongs to one (scale, flip) pair: geom[8k .. 8k+7] = Hs_k, Ws_k (the
+ * scaled image size), ch_k, cw_k (the effective crop), sh_k, sw_k (the effective stride; both already clamped, 1 <= stride <= crop <=
+ * scaled size per axis), h_k, w_k (the size of ONE window's low-resolution map); flip[k] != 0: the set holds the model's outputs
+ * for the windows of the MIRRORED scaled image.  The grid of set k is segf_slide_grid(Hs_k, Ws_k, ch_k, cw_k, sh_k, sw_k) -> ny_k,
+ * nx_k; logits[k]: ONE device buffer [B][ny_k nx_k][h_k][w_k][ldl_k >= C], image-major, then window order -- exactly the layout
+ * segf_slide_argmax_confmat reads.  logits / geom / ldl / flip are HOST arrays of n entries: the library copies them into a by-value
+ * kernel argument of SEGF_MSF_MAX_MAPS entries -- no device table, no upload, no host synchronisation (the call can be captured into
+ * a hipGraph; the host arrays may be freed on return).  64-bit indexing throughout.
+ * For every output pixel (b, Y, X), for every set k in list order:
+ *   outer taps (Hs_k, Ws_k) == (H, W): the single scaled pixel (Y, X).  Otherwise the source rows / columns / lambdas y0, y1, ly and
+ *              x0, x1, lx of F.interpolate(size=(H, W), mode='bilinear', align_corners=False) from (Hs_k, Ws_k) at ANY ratio (Hs_k > H
+ *              too: downsampling without antialiasing).  Flip rule: for flip[k] != 0 the tap columns are read at Ws_k-1-x0, Ws_k-1-x1
+ *              (same size: at Ws_k-1-X) with the same weights -- exactly the sample of the un-mirrored mean map; no mirrored copy is
+ *              made.
+ *   window mean at each tap (ys, xs), the arithmetic of segf_slide_argmax_confmat on the scaled image: over every window of set k
+ *              that covers (ys, xs), in ascending (i, j) order, the bilinear sample of that window's map at the local pixel (four taps
+ *              in ATen's operation order; h_k == ch_k and w_k == cw_k: the row is read directly), summed in fp32 in window order and
+ *              divided by the cover count with a true IEEE fp32 division.
+ *   logit      z_k[c] = the four means M00, M01, M10, M11 combined with ly, lx in ATen's operation order, fma(M11, w11, fma(M10, w10,
+ *              fma(M00, w00, M01 w01))); same size: the one mean itself.
+ *   softmax    p_k = softmax_c(z_k), fp32, max-subtracted.
+ *   sum        S[c] = p_0[c] + p_1[c] + ... + p_(n-1)[c], added in set order (summation order = the order of the arrays): two runs
+ *              give the same bits; a permutation of the sets may change the last bits.
+ * After the last set:
+ *   arg max    pred = the lowest class index attaining max_c S[c] (0 on an all-NaN row).
+ *   count      as segf_argmax_confmat: mat += 1 at [t][pred] where 0 <= t < C; hist the same except t == ignore_label; a label outside
+ *              [0, C) that is not ignore_label sets flag[0] bit 0 and is counted nowhere.  target == NULL: no counting (inference).
+ *              A pixel counted nowhere is skipped when neither output below is wanted.
+ * pred_out (nullable): int64 [B][H][W].  prob_out (nullable): fp32 [B*H*W][ldp >= C], the sums S (NOT divided by n).
+ * SEGF_ERR_SHAPE before any launch: n < 1 or n > SEGF_MSF_MAX_MAPS, C < 1 or C > 192, B < 1 or B > 65535, H or W < 1, any set with
+ * 1 <= sh_k <= ch_k <= Hs_k or 1 <= sw_k <= cw_k <= Ws_k violated or h_k, w_k < 1, ldl_k < C, prob_out given with ldp < C, a NULL
+ * array or a NULL logits[k]; SEGF_ERR_DTYPE for an unknown dt.  segf_msf_slide_supported: 1 when the shape part of that (without the
+ * row strides and pointers) and dt are acceptable, else 0.
+ * Cost: up to four window means per set and pixel, each up to four tap rows per covering window, served from cache; the labels once;
+ * the counts.  No floating-point atomics.  Measured figures in profiles/msf_slide_eval.md.                                  */
+int segf_msf_slide_supported(int dt, int B, int C, int n, const int* geom /*HOST [n][8]*/, int H, int W);
+int segf_msf_slide_argmax_confmat(int dt, int B, int C, int n,
+                                  void** logits       /*HOST array of n device pointers*/,
+                                  const int* geom     /*HOST [n][8] = Hs, Ws, ch, cw, sh, sw, h, w*/,
+                                  const int64_t* ldl  /*HOST [n]*/,
+                                  const int* flip     /*HOST [n]*/,
+                                  int H, int W, const int64_t* target, int64_t ignore_label,
+                                  int64_t* mat, int64_t* hist, int32_t* flag,
+                                  int64_t* pred_out /*nullable*/, float* prob_out /*nullable*/, int64_t ldp, void* stream);
+
 /* out[r] = argmax_c x[r][c] (lowest index on ties): the prediction step of single-image inference
  * (estimate_model.py:104-106, softmax(dim=1).argmax(dim=1) -- softmax is monotonic).  x: [rows][ld >= C], C <= 192. */
 int segf_argmax_rows(int dt, int64_t rows, int C, const void* x, int64_t ld, int64_t* out, void* stream);

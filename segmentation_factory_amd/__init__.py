@@ -8,7 +8,7 @@ Importing the package does not load the shared library; the first kernel call do
 is missing.
 """
 from .build_models import SegmentationModel, head_dict, backbone_registry, register_backbone, register_head  # noqa: F401
-from .engine import criterion, criterion_lowres, evaluate, evaluate_msf, evaluate_slide, msf_sizes, slide_windows, train_one_epoch  # noqa: F401
+from .engine import criterion, criterion_lowres, evaluate, evaluate_msf, evaluate_msf_slide, evaluate_slide, msf_sizes, slide_windows, train_one_epoch  # noqa: F401
 from .metrics import Metrics  # noqa: F401
 from .losses import CrossEntropy, OhemCrossEntropy, FocalLoss, get_loss  # noqa: F401   (util/losses.py's classes)
 from .inference import SemSeg  # noqa: F401   (estimate_model.py's SemSeg for tensors)

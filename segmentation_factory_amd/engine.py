@@ -440,18 +440,133 @@ def _evaluate_slide(args, model, core, fused, dataloader, device, print_freq, wr
 
 
 @torch.inference_mode()
+def evaluate_msf_slide(args, model, dataloader, device, print_freq, writer=None, scales=MSF_SCALES, flip=True, crop=512, stride=None,
+                       window_batch=None):
+    """Multi-scale + flip sliding-window evaluation (mmseg's aug_test with mode='slide', the protocol behind SegFormer's multi-scale
+    Cityscapes figures): every batch is resized to each of `scales` (sizes: msf_sizes), with `flip` also horizontally mirrored; each
+    of those images is cut into overlapping `crop` windows at `stride` (slide_windows on the scaled size; stride None: floor(2 crop /
+    3)), the model runs on the windows, the logits of overlapping windows are averaged, the mean is resized to the label size and
+    softmaxed, the probabilities of all (scale, flip) pairs are summed and the arg max of the sum is scored.  Returns (confmat, metric)
+    like `evaluate`, with the same eval-dtype switch, buffer broadcast and reductions.  The resize and the window slices of the
+    3-channel input are torch ops; everything after the forwards is ONE kernel per batch (Metrics.update_msf_slide): no
+    full-resolution logits, accumulator, count map or probability map exists, at the label size or at a scaled size.
+
+    window_batch None: all B nWin windows of a (scale, flip) pair go through one forward.  An integer: chunks of at most that many.
+    Aliasing (wider than in evaluate_msf / evaluate_slide): a GraphedEvalSession replays one graph per input shape and hands back that
+    graph's STATIC output buffer, and the full-size windows of ALL scales, straight and mirrored, share one shape.  Every forward's
+    result is therefore copied into its slot of a buffer kept per (set index, shape) for the whole evaluation (no allocation per step
+    after the first batch of a shape) before the next replay."""
+    model.eval()
+    metric = Metrics(args.nb_classes, args.ignore_label, device)
+    confmat = utils.ConfusionMatrix(args.nb_classes)
+    metric_logger = utils.MetricLogger(delimiter="  ")
+    core = model.module if hasattr(model, 'module') else model
+    fused = hasattr(core, 'forward_lowres')
+    eval_dtype = EVAL_DTYPES[str(getattr(args, 'eval_dtype', None) or 'fp32')]
+    trained_dtype = getattr(core, 'compute_dtype', None)
+    switch = hasattr(core, 'set_compute_dtype') and trained_dtype is not None and trained_dtype != eval_dtype
+    if switch:
+        core.set_compute_dtype(eval_dtype)
+    try:
+        return _evaluate_msf_slide(args, model, core, fused, dataloader, device, print_freq, writer, metric, confmat, metric_logger,
+                                   tuple(scales), bool(flip), hip.hw_pair(crop, 'crop'),
+                                   hip.hw_pair(stride, 'stride') if stride is not None else default_slide_stride(crop), window_batch)
+    finally:
+        if switch:
+            core.set_compute_dtype(trained_dtype)
+
+
+def _evaluate_msf_slide(args, model, core, fused, dataloader, device, print_freq, writer, metric, confmat, metric_logger, scales, flip,
+                        crop, stride, window_batch):
+    if not scales or len(scales) * (2 if flip else 1) > hip.MSF_MAX_MAPS:
+        raise ValueError(f'evaluate_msf_slide: 1 .. {hip.MSF_MAX_MAPS} window sets per image ({len(scales)} scales, flip={flip})')
+    if window_batch is not None and int(window_batch) < 1:
+        raise ValueError(f'evaluate_msf_slide: window_batch must be at least 1, got {window_batch}')
+    if utils.get_world_size() > 1:
+        from .graph import broadcast_buffers_
+        broadcast_buffers_(core)                                  # as _evaluate: the forwards below bypass the DDP wrapper
+    session = None
+    graph_pref = getattr(args, 'hip_graph', None)
+    if (graph_pref is None or bool(graph_pref)) and fused and torch.device(device).type == 'cuda':
+        from .graph import GraphedEvalSession
+        # per scale at most a clamped crop, hence a chunk shape and a remainder shape of its own
+        session = GraphedEvalSession(core, max_graphs=max(8, 2 * len(scales)), max_captures=max(8, 2 * len(scales)))
+    kept = {}                                                     # (set index, rows, columns, dtype) -> that set's windows (see the docstring)
+
+    def forward(x):
+        if fused:
+            return session(x) if (session is not None and x.is_cuda) else core.forward_lowres(x)
+        out = model(x)
+        return tokens_from_nchw(out, out.dtype if out.dtype in (torch.float32, torch.bfloat16) else torch.float32)
+
+    def run_windows(k, x):
+        """Head outputs of the windows x of set k as (rows, h, w): one forward, or chunks of window_batch, each copied out of the
+        graph's static buffer into the set's own buffer before the next replay."""
+        n = x.shape[0]
+        step = n if window_batch is None else min(int(window_batch), n)
+        if step == n and not (session is not None and x.is_cuda):
+            lo = forward(x)                                       # eager and whole: a fresh tensor, nothing to alias
+            return lo.data, lo.H, lo.W
+        buf = None
+        for a in range(0, n, step):
+            lo = forward(x[a:a + step])
+            per = lo.H * lo.W                                     # rows per window
+            if buf is None:
+                key = (k, n * per, lo.data.shape[1], lo.data.dtype)
+                buf = kept.get(key)
+                if buf is None:
+                    buf = kept[key] = torch.empty((n * per, lo.data.shape[1]), dtype=lo.data.dtype, device=lo.data.device)
+            buf[a * per:a * per + lo.data.shape[0]].copy_(lo.data)
+        return buf, lo.H, lo.W
+
+    for idx, (images, labels) in enumerate(metric_logger.log_every(dataloader, print_freq, 'Test (slide-MSF):')):
+        images = images.to(device, non_blocking=True)
+        labels = labels.to(device, non_blocking=True)
+        B = images.shape[0]
+        H, W = images.shape[2:]
+        sets, flips = [], []
+        for size in msf_sizes(H, W, scales):
+            xs = images if size == (H, W) else torch.nn.functional.interpolate(images, size=size, mode='bilinear', align_corners=False)
+            (ch, cw), strd, origins = slide_windows(size[0], size[1], crop, stride)
+            for f in ((0, 1) if flip else (0,)):
+                src = xs.flip(3) if f else xs
+                # image-major, then window order: the layout segf_msf_slide_argmax_confmat reads
+                x = torch.stack([src[:, :, y:y + ch, x0:x0 + cw] for y, x0 in origins], dim=1).reshape(B * len(origins), src.shape[1], ch, cw)
+                sets.append((run_windows(len(sets), x), size, (ch, cw), strd))
+                flips.append(f)
+        metric.update_msf_slide(sets, flips, labels, (H, W), confmat=confmat)      # one pass: every set, both matrices
+        if writer and idx % print_freq == 0:
+            writer.add_scalar('valid_mf1', metric.compute_f1()[1])
+            writer.add_scalar('valid_acc', metric.compute_pixel_acc()[1])
+            writer.add_scalar('valid_mIOU', metric.compute_iou()[1])
+    confmat.reduce_from_all_processes()
+    metric.reduce_from_all_processes()
+    return confmat, metric
+
+
+@torch.inference_mode()
 def evaluate(args, model, dataloader, device, print_freq, writer=None):
     """engine.py:74-104.  The reference evaluates in fp32 with autocast deliberately off (engine.py:86-88), whatever precision it
     trained in -- so does this: the forward runs the exact-fp32 kernels unless `args.eval_dtype == 'bf16'` (train_gpu.py
     --eval-dtype bf16: the production storage type, ~5x the rate; tests/test_model_gpu.py measures what it flips).
     `args.eval_scales` (non-empty) or `args.eval_flip` hand the call to evaluate_msf; without them nothing here changes.
     `args.eval_mode == 'slide'` hands it to evaluate_slide (args.eval_crop, default args.image_size; args.eval_stride, default
-    floor(2 crop / 3); args.eval_window_batch); sliding windows at several scales or mirrored are not built: ValueError."""
+    floor(2 crop / 3); args.eval_window_batch); in that mode sliding windows at several scales or mirrored are not built: ValueError.
+    `args.eval_mode == 'slide-msf'` is the mode that has them: evaluate_msf_slide, crop / stride / window batch read as in 'slide',
+    scales / flip as for evaluate_msf."""
+    if getattr(args, 'eval_mode', 'whole') == 'slide-msf':
+        crop = getattr(args, 'eval_crop', None) or getattr(args, 'image_size', None)
+        if crop is None:
+            raise ValueError("evaluate: eval_mode 'slide-msf' needs args.eval_crop (or args.image_size)")
+        return evaluate_msf_slide(args, model, dataloader, device, print_freq, writer,
+                                  scales=tuple(getattr(args, 'eval_scales', None) or (1.0,)), flip=bool(getattr(args, 'eval_flip', False)),
+                                  crop=crop, stride=getattr(args, 'eval_stride', None),
+                                  window_batch=getattr(args, 'eval_window_batch', None))
     if getattr(args, 'eval_mode', 'whole') == 'slide':
         scales = tuple(getattr(args, 'eval_scales', None) or (1.0,))
         if scales != (1.0,) or getattr(args, 'eval_flip', False):
             raise ValueError("evaluate: eval_mode 'slide' with eval_scales other than (1.0,) or with eval_flip -- sliding windows at "
-                             'several scales or mirrored are not built')
+                             "several scales or mirrored are not built in this mode; use eval_mode 'slide-msf'")
         crop = getattr(args, 'eval_crop', None) or getattr(args, 'image_size', None)
         if crop is None:
             raise ValueError("evaluate: eval_mode 'slide' needs args.eval_crop (or args.image_size)")

@@ -1827,6 +1827,51 @@ def slide_argmax_confmat(windows, B, Cc, H, W, crop, stride, target, ignore_labe
                                          mean_out.stride(0) if mean_out is not None else 0, _stream()), 'segf_slide_argmax_confmat')
 
 
+def msf_slide_argmax_confmat(window_sets, flips, B, Cc, H, W, target, ignore_label, mat, hist, flag, pred_out=None, prob_out=None):
+    """segf_msf_slide_argmax_confmat: multi-scale + flip sliding-window evaluation in one kernel.  window_sets: one entry per
+    (scale, flip) pair, `(windows, (Hs, Ws), crop, stride)` -- windows a TokenMap (or a (rows, h, w) tuple) holding the head outputs
+    of all windows of the batch cut from the (Hs, Ws) scaled image, rows = [B*ny*nx*h*w, >= Cc] with unit inner stride, image-major,
+    then window order (slide_grid(Hs, Ws, crop, stride) gives ny, nx; crop / stride already clamped as engine.slide_windows does), all
+    sets one dtype; flips: one flag per set (the set belongs to the mirrored image).  Per pixel of the (H, W) output and per set: the
+    window mean of slide_argmax_confmat at the taps of the resize from (Hs, Ws), softmax, sum in list order, arg max -> mat / hist /
+    flag as argmax_confmat (target None: no counting), pred_out int64 [B, H, W], prob_out fp32 [B*H*W, >= Cc] = the summed
+    probabilities.  The descriptors go by value through host arrays: nothing is uploaded, so the call can be captured."""
+    n = len(window_sets)
+    if len(flips) != n:
+        raise ValueError(f'msf_slide_argmax_confmat: {n} window sets but {len(flips)} flip flags')
+    rows, geom = [], []
+    for k, (windows, (Hs, Ws), crop, stride) in enumerate(window_sets):
+        (ch, cw), (sh, sw) = hw_pair(crop, 'crop'), hw_pair(stride, 'stride')
+        ny, nx = slide_grid(Hs, Ws, (ch, cw), (sh, sw))
+        data, h, w = (windows.data, windows.H, windows.W) if hasattr(windows, 'data') else windows
+        h, w = int(h), int(w)
+        _need_cuda(data)
+        if data.ndim != 2 or data.stride(1) != 1 or data.shape[0] != B * ny * nx * h * w or data.shape[1] < Cc:
+            raise ValueError(f'msf_slide_argmax_confmat: set {k} must be [B*ny*nx*h*w, >=C] rows with unit inner stride '
+                             f'(B {B}, grid {ny} x {nx}, map {h} x {w}, C {Cc}; got {tuple(data.shape)}, strides {tuple(data.stride())})')
+        if hasattr(windows, 'B') and windows.B != B * ny * nx:
+            raise ValueError(f'msf_slide_argmax_confmat: set {k} holds {windows.B} window maps, expected B*ny*nx = {B * ny * nx}')
+        if rows and data.dtype != rows[0].dtype:
+            raise ValueError('msf_slide_argmax_confmat: the window sets must share one dtype')
+        rows.append(data)
+        geom += [int(Hs), int(Ws), ch, cw, sh, sw, h, w]
+    _need_cuda(target, mat, hist, flag, pred_out, prob_out)
+    if target is not None:
+        assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == B * H * W
+        assert all(t.dtype == torch.int64 and t.is_contiguous() and t.numel() == Cc * Cc for t in (mat, hist)) and flag.dtype == torch.int32
+    assert pred_out is None or (pred_out.dtype == torch.int64 and pred_out.is_contiguous() and pred_out.numel() == B * H * W)
+    assert prob_out is None or (prob_out.dtype == torch.float32 and prob_out.ndim == 2 and prob_out.stride(1) == 1
+                                and prob_out.shape[0] == B * H * W and prob_out.shape[1] >= Cc)
+    ptrs = (C.c_void_p * max(n, 1))(*[r.data_ptr() for r in rows])
+    c_geom = (C.c_int * max(8 * n, 1))(*geom)
+    c_ld = (C.c_int64 * max(n, 1))(*[r.stride(0) for r in rows])
+    c_fl = (C.c_int * max(n, 1))(*[1 if f else 0 for f in flips])
+    _chk(lib().segf_msf_slide_argmax_confmat(dt_of(rows[0]) if rows else F32, B, Cc, n, ptrs, c_geom, c_ld, c_fl, H, W, _ptr(target),
+                                             int(ignore_label), _ptr(mat), _ptr(hist), _ptr(flag), _ptr(pred_out), _ptr(prob_out),
+                                             prob_out.stride(0) if prob_out is not None else 0, _stream()),
+         'segf_msf_slide_argmax_confmat')
+
+
 def confmat_pairs(gt, pred, Cc, ignore_label, mat, hist, flag):
     _need_cuda(gt, pred)
     _chk(lib().segf_confmat_pairs(_ptr(gt), _ptr(pred), gt.numel(), Cc, int(ignore_label), _ptr(mat), _ptr(hist),

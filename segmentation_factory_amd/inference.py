@@ -134,15 +134,53 @@ class SemSeg:
             seg = seg[:, iy][:, :, ix]
         return seg.squeeze(0), self._colour(seg, orig_img, overlay)
 
-    def predict(self, image: torch.Tensor, overlay: bool = True, scales=None, flip: bool = False, slide=None):
+    @torch.inference_mode()
+    def predict_msf_slide(self, x: torch.Tensor, orig_hw, crop, stride, scales, flip, orig_img=None, overlay=False):
+        """Multi-scale + flip sliding-window prediction of the preprocessed image x: at every scale (engine.msf_sizes of x's size),
+        straight and -- with `flip` -- mirrored, the model runs on the overlapping windows of engine.slide_windows of the scaled image;
+        per (scale, flip) pair the windows' logits are averaged, the mean is resampled to x's size and softmaxed, the probabilities
+        are summed and the arg max of the sum is taken -- one kernel (hip.msf_slide_argmax_confmat without labels), its pred_out is
+        the segmentation map at x's size; an original size that differs is reached by nearest-neighbour lookup of the class indices,
+        as in predict_slide."""
+        from .engine import default_slide_stride, msf_sizes, slide_windows
+        B, _, H1, W1 = x.shape
+        stride = stride if stride is not None else default_slide_stride(crop)
+        sets, flips = [], []
+        for size in msf_sizes(H1, W1, tuple(scales) if scales else (1.0,)):
+            xs = x if size == (H1, W1) else torch.nn.functional.interpolate(x, size=size, mode='bilinear', align_corners=False)
+            (ch, cw), strd, origins = slide_windows(size[0], size[1], crop, stride)
+            for f in ((0, 1) if flip else (0,)):
+                src = xs.flip(3) if f else xs
+                win = torch.stack([src[:, :, y:y + ch, x0:x0 + cw] for y, x0 in origins], dim=1).reshape(B * len(origins), x.shape[1], ch, cw)
+                sets.append((self.model_forward(win), size, (ch, cw), strd))
+                flips.append(f)
+        lo = sets[0][0]
+        nc = self.model.num_classes if hasattr(self.model, 'num_classes') else lo.data.shape[1]
+        seg = torch.empty((B, H1, W1), dtype=torch.int64, device=lo.data.device)
+        hip.msf_slide_argmax_confmat(sets, flips, B, nc, H1, W1, None, -1, None, None, None, pred_out=seg)
+        H0, W0 = orig_hw
+        if (H0, W0) != (H1, W1):
+            iy = (torch.arange(H0, device=seg.device) * H1) // H0
+            ix = (torch.arange(W0, device=seg.device) * W1) // W0
+            seg = seg[:, iy][:, :, ix]
+        return seg.squeeze(0), self._colour(seg, orig_img, overlay)
+
+    def predict(self, image: torch.Tensor, overlay: bool = True, scales=None, flip: bool = False, slide=None, msf_slide=None):
         """image: uint8 CHW tensor (what torchvision.io.read_image returns).  -> (seg_map, colour image or None).
         scales (e.g. (0.5, 0.75, 1.0, 1.25, 1.5, 1.75)) and / or flip: multi-scale + flip prediction (postprocess_msf); slide =
         (crop, stride) (stride None: floor(2 crop / 3)): sliding-window prediction (predict_slide), not together with scales / flip;
-        without them the single forward of the reference."""
+        msf_slide = (crop, stride): sliding windows at every one of `scales` (default (1.0,)) and, with `flip`, mirrored
+        (predict_msf_slide), not together with slide; without them the single forward of the reference."""
+        if msf_slide is not None and slide is not None:
+            raise ValueError('SemSeg.predict: msf_slide together with slide -- give one of them')
         if slide is not None and (scales or flip):
             raise ValueError('SemSeg.predict: slide together with scales / flip -- sliding windows at several scales or mirrored are '
-                             'not built')
+                             'not built for slide=; use msf_slide=(crop, stride)')
         x = self.preprocess(image)
+        if msf_slide is not None:
+            crop, stride = msf_slide
+            return self.predict_msf_slide(x, tuple(image.shape[1:]), crop, stride, tuple(scales) if scales else (1.0,), bool(flip), image,
+                                          overlay)
         if slide is not None:
             crop, stride = slide
             return self.predict_slide(x, tuple(image.shape[1:]), crop, stride, image, overlay)

@@ -5,7 +5,8 @@ ground truth.  Counting happens on device: ``update`` takes materialised NCHW lo
 ``update_lowres`` takes the head output and fuses upsample + argmax + histogram in one kernel; ``update_msf`` takes the head outputs
 of one batch at several scales / mirrored (multi-scale + flip evaluation) and fuses resample + softmax + sum + argmax + histogram;
 ``update_slide`` takes the head outputs of the overlapping crops of one batch (sliding-window evaluation) and fuses resample + mean
-over the covering windows + argmax + histogram.
+over the covering windows + argmax + histogram; ``update_msf_slide`` takes such window outputs at several scales / mirrored and fuses
+window mean + resample + softmax + sum + argmax + histogram.
 """
 import torch
 import torch.distributed as dist
@@ -86,6 +87,20 @@ class Metrics:
         data = lowres_windows.data if hasattr(lowres_windows, 'data') else lowres_windows[0]
         counts, flag, mat, target = self._count_targets(data.device, target, confmat)
         hip.slide_argmax_confmat(lowres_windows, target.numel() // (H * W), n, H, W, crop, stride, target, self.ignore_label, mat, counts, flag)
+        hip.hist_accum_(self.hist, counts)
+
+    def update_msf_slide(self, window_sets, flips, target: torch.Tensor, size, confmat=None):
+        """Multi-scale + flip sliding-window counting: `window_sets[k] = (windows, (Hs, Ws), crop, stride)` holds the head outputs of
+        every window of one batch cut from the image at one scale (layout and clamping as update_slide / engine.slide_windows),
+        `flips[k]` says that set k belongs to the horizontally mirrored image.  One kernel takes, per set, the window mean at the taps
+        of the resize to `size`, softmaxes, sums the probabilities in list order, takes the arg max and counts -- the same static
+        scratch, the same hist_accum_ and the same one-pass feeding of both matrices as update_slide; no full-resolution map exists."""
+        H, W = size
+        n = self.num_classes
+        first = window_sets[0][0]
+        data = first.data if hasattr(first, 'data') else first[0]
+        counts, flag, mat, target = self._count_targets(data.device, target, confmat)
+        hip.msf_slide_argmax_confmat(window_sets, flips, target.numel() // (H * W), n, H, W, target, self.ignore_label, mat, counts, flag)
         hip.hist_accum_(self.hist, counts)
 
     def _finish(self, v):

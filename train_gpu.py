@@ -132,20 +132,24 @@ def get_args_parser():
                         help="precision of evaluate()'s forward: fp32 as the reference (engine.py:86-88 switches autocast off), or the "
                              'bf16 production storage type')
     parser.add_argument('--eval-scales', dest='eval_scales', nargs='+', type=float, default=None,
-                        help='multi-scale evaluation (--eval and the per-epoch validation): run the model at these scales of the input '
-                             '(e.g. 0.5 0.75 1.0 1.25 1.5 1.75), sum the class probabilities, score the arg max of the sum')
+                        help='multi-scale evaluation (--eval and the per-epoch validation; read by --eval-mode whole and slide-msf, '
+                             'refused by slide): run the model at these scales of the input (e.g. 0.5 0.75 1.0 1.25 1.5 1.75), sum the '
+                             'class probabilities, score the arg max of the sum')
     parser.add_argument('--eval-flip', dest='eval_flip', action='store_true', default=False,
-                        help='evaluation also runs every scale on the horizontally mirrored image (with --eval-scales: the MSF protocol)')
-    parser.add_argument('--eval-mode', dest='eval_mode', default='whole', choices=['whole', 'slide'],
+                        help='evaluation also runs every scale on the horizontally mirrored image (with --eval-scales: the MSF protocol; '
+                             'read by --eval-mode whole and slide-msf, refused by slide)')
+    parser.add_argument('--eval-mode', dest='eval_mode', default='whole', choices=['whole', 'slide', 'slide-msf'],
                         help='evaluation (--eval and the per-epoch validation) on the whole image, or sliding-window: the model runs on '
                              'overlapping --eval-crop windows at --eval-stride, the logits of overlapping windows are averaged and the arg '
-                             'max of the mean is scored')
+                             'max of the mean is scored; slide-msf: sliding windows at every one of --eval-scales, with --eval-flip also '
+                             'mirrored, the class probabilities of the window means summed')
     parser.add_argument('--eval-crop', dest='eval_crop', nargs='+', type=int, default=None, metavar='N',
-                        help='--eval-mode slide: window size H [W] (default: --image_size); clamped to the image')
+                        help='--eval-mode slide / slide-msf: window size H [W] (default: --image_size); clamped to the (scaled) image')
     parser.add_argument('--eval-stride', dest='eval_stride', nargs='+', type=int, default=None, metavar='N',
-                        help='--eval-mode slide: window stride H [W] (default: floor(2 crop / 3) per axis, 512 -> 341)')
+                        help='--eval-mode slide / slide-msf: window stride H [W] (default: floor(2 crop / 3) per axis, 512 -> 341)')
     parser.add_argument('--eval-window-batch', dest='eval_window_batch', type=int, default=None, metavar='N',
-                        help='--eval-mode slide: forward at most N windows at once (default: all windows of a batch)')
+                        help='--eval-mode slide / slide-msf: forward at most N windows at once (default: all windows of a batch; slide-msf: '
+                             'of a batch at one scale)')
     parser.add_argument('--loss', default='ce_dice', choices=['ce_dice', 'CrossEntropy', 'OhemCrossEntropy', 'FocalLoss'],
                         help="training loss: ce_dice = the reference engine's criterion (CE + Dice, see --dice), or one of the classes of "
                              'util/losses.py on the fused low-resolution loss path (segmentation_factory_amd/losses.py; --dice is not consulted)')
