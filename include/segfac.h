@@ -943,6 +943,48 @@ int64_t segf_input_train_scaled_ws(int B, int H, int W, int kmax);
 int segf_input_train_scaled(const segf_input_scaled_sample* samples /*host [B]*/, int B, int H, int W, int kmax, void* ws,
                             const float* mean3, const float* std3, const int64_t* label_lut, float* out_img, int64_t* out_lbl,
                             void* stream);
+/* Class-balanced crop choice: mmsegmentation's RandomCrop(crop_size, cat_max_ratio) in front of either training stack.  In words,
+ * mmseg's loop is: draw a crop window; if cat_max_ratio < 1, up to ten times: crop the label map to the window, count its values
+ * with np.unique(..., return_counts=True), drop the ignore index, and stop if more than one class is left and
+ * np.max(cnt) / np.sum(cnt) < cat_max_ratio; otherwise draw another window.  After ten failed tests the window drawn last -- the
+ * eleventh -- is used as it comes, without a test.  The random draws stay with the caller (transforms.py); the kernels see K =
+ * tries + 1 candidate windows (top_k, left_k), k = 0 .. K-1, per sample, each H x W, and apply THE RULE:
+ *   - every window pixel gives its raw uint8 label v exactly as the crop kernels read it.  Unscaled stack: lbl[top + y][left + x],
+ *     and raw 0 outside the source (Image.crop).  Scaled stack: Pillow's NEAREST-resized label at resized coordinates (top + y,
+ *     left + x) -- the source index is ImagingScaleAffine's, accumulated in double from output index 0, as in segf_input_train_scaled
+ *     -- and label_fill outside [0, res_h) x [0, res_w);
+ *   - c = label_lut[v] is its class (identity when the table is null); pixels with c == ignore_class are not counted; two raw values
+ *     that the table maps to one class are one class;
+ *   - with n_c the remaining counts, window k PASSES iff at least two classes have n_c > 0 AND
+ *     (double)max_c n_c / (double)sum_c n_c < max_ratio -- strict, in double, like numpy's in mmseg.  A window with no counted pixel
+ *     fails, and no division happens;
+ *   - chosen[b] = the first passing k among 0 .. K-2; if none passes, K-1, which is used UNTESTED (ten tests, then the eleventh
+ *     draw is taken as it comes).  With K == 1 the result is 0 and no label is read.
+ * The horizontal flip and the colour jitter come after the crop and play no part.  The choice is made on the device: one workgroup
+ * per sample walks the windows in order and stops at the first pass; nothing is read back, nothing is synchronised.  The counts are
+ * integers (integer LDS adds only), so two runs give the same bits.  chosen (nullable) is written for every sample.
+ *
+ * segf_input_crop_select: the unscaled stack.  Rewrites top / left of the DEVICE records in place with the chosen candidate's; an
+ * unchanged segf_input_train on the same records follows on the same stream.  cand: DEVICE int32 [B][K][2] = (top, left); they are
+ * not read on the host, and like the top / left of segf_input_train they must not be negative.
+ * SEGF_ERR_SHAPE, before any launch and with the outputs untouched: K < 1 or K > 32; max_ratio not in (0, 1] or NaN; a null samples /
+ * cand; samples not 16-byte aligned or cand not 4-byte aligned; H * W > 2^30.  A candidate with |top| or |left| > 2^30 cannot be
+ * refused here, because the candidates are not read on the host: the caller bounds them (transforms.py `pack` does).
+ *
+ * segf_input_train_scaled_select: segf_input_train_scaled with the choice in front.  samples and cand are HOST arrays, uploaded
+ * into ws as segf_input_train_scaled uploads its records (one wait for the stream, both arrays reusable on return); cand holds
+ * RESIZED coordinates and may be negative.  The selection kernel runs BEFORE the coefficient-table kernel, because those tables
+ * depend on the window; it patches top / left of the uploaded records (the records' own top / left are checked and then replaced),
+ * then segf_input_train_scaled's own kernels run.  ws: segf_input_train_scaled_select_ws(B, H, W, kmax, K) BYTES, 16-byte aligned:
+ * segf_input_train_scaled_ws plus the candidates; it grows with K and does not depend on any source or resized size.
+ * SEGF_ERR_SHAPE as above, for a candidate with |top| or |left| > 2^30, and for whatever segf_input_train_scaled refuses. */
+int segf_input_crop_select(segf_input_sample* samples, const int32_t* cand, int B, int K, int H, int W, double max_ratio,
+                           const int64_t* label_lut, int64_t ignore_class, int32_t* chosen, void* stream);
+int64_t segf_input_train_scaled_select_ws(int B, int H, int W, int kmax, int K);
+int segf_input_train_scaled_select(const segf_input_scaled_sample* samples, const int32_t* cand, int K, double max_ratio,
+                                   int64_t ignore_class, int32_t* chosen, int B, int H, int W, int kmax, void* ws,
+                                   const float* mean3, const float* std3, const int64_t* label_lut, float* out_img,
+                                   int64_t* out_lbl, void* stream);
 /* segf_input_val: ExtResize -> ExtToTensor -> ExtNormalize (build_datasets.py:24-29; extra_transform.py:395-419) for ONE image:
  * Image.resize((out_w, out_h), BILINEAR) = ImagingResample's horizontal then vertical pass in 22-bit fixed point, each rounded to
  * uint8, and Image.resize(..., NEAREST) for the label (ImagingScaleAffine's accumulated source index); the caller computes

@@ -452,6 +452,223 @@ __global__ void __launch_bounds__(256) input_scale_crop_kernel(int H, int W, int
     }
 }
 
+// ---- class-balanced crop choice: the rule of include/segfac.h (segf_input_crop_select) ---------------------------------------------
+// One workgroup of 16 waves per sample walks the candidate windows IN ORDER and stops at the first that passes, so a batch whose
+// first windows pass reads each label once, and nothing but the chosen index leaves the workgroup: no workspace, no second launch,
+// no host read.  Counting: a lane takes 16 consecutive window pixels of one row and forms runs of equal bytes in registers; label
+// maps are piecewise constant, so almost every lane ends with ONE run, and when the 64 runs of a wave carry the same value (the
+// all-road window, where every lane would hit the same counter) they are summed across the wave by shuffles and added once.
+// Anything else goes to the wave's OWN 256 raw-value counters in LDS by ds_add_u32, one add per run.  The counters are integers:
+// the verdict does not depend on the order of the adds.  At the end of a window the 16 x 256 counters are merged, raw values that
+// label_lut maps to one class are added up, and the test itself is one double division.
+constexpr int SEL_THREADS = 1024, SEL_WAVES = SEL_THREADS / 64, SEL_SEG = 16;
+
+struct SelectShared {
+    unsigned hist[SEL_WAVES][256];                                        // per wave, per raw uint8 value
+    long long cls[256];                                                   // label_lut (identity when null)
+    unsigned raw[256];                                                    // the merged counters of the window
+    unsigned ncls, maxc, sum;                                             // over the counted classes
+};
+
+// The final run (cur, run) of every lane of a wave -> the wave's counters.  Called by all 64 lanes; lanes without work carry
+// run == 0, and they are the LAST lanes of the wave (work indices ascend with the lane), so lane 0's value stands for the wave.
+__device__ __forceinline__ void select_flush(unsigned* __restrict__ h, int cur, int run) {
+    const int first = __shfl(cur, 0, 64);
+    if (__all(run == 0 || cur == first)) {
+        int s = run;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if ((threadIdx.x & 63) == 0 && s) atomicAdd(&h[first], (unsigned)s);
+    } else if (run) {
+        atomicAdd(&h[cur], (unsigned)run);
+    }
+}
+
+// Counts one H x W window.  load(y, x0, n, d): the raw labels of window pixels (y, x0 .. x0 + n - 1), n <= 16, one per byte of d[4]
+// (bytes past n are zero).
+template <class Load>
+__device__ __forceinline__ void select_count(unsigned* __restrict__ h, int H, int W, const Load& load) {
+    const int segs = (W + SEL_SEG - 1) / SEL_SEG;
+    const int64_t total = (int64_t)H * segs;
+    for (int64_t base = 0; base < total; base += SEL_THREADS) {           // workgroup-uniform trip count: select_flush needs whole waves
+        const int64_t idx = base + threadIdx.x;
+        int cur = -1, run = 0;
+        if (idx < total) {
+            const int y = (int)(idx / segs), x0 = (int)(idx - (int64_t)y * segs) * SEL_SEG;
+            const int n = W - x0 < SEL_SEG ? W - x0 : SEL_SEG;
+            unsigned d[4];
+            load(y, x0, n, d);
+            cur = (int)(d[0] & 255u);
+            const unsigned rep = (unsigned)cur * 0x01010101u;
+            if (n == SEL_SEG && d[0] == rep && d[1] == rep && d[2] == rep && d[3] == rep) {
+                run = SEL_SEG;
+            } else {
+                run = 1;
+#pragma unroll
+                for (int k = 1; k < SEL_SEG; ++k)
+                    if (k < n) {
+                        const int v = (int)((d[k >> 2] >> (8 * (k & 3))) & 255u);
+                        if (v == cur) ++run;
+                        else { atomicAdd(&h[cur], (unsigned)run); cur = v; run = 1; }
+                    }
+            }
+        }
+        select_flush(h, cur, run);
+    }
+}
+
+// unscaled stack: window pixel (y, x) is lbl[top + y][left + x], raw 0 outside the source (Image.crop)
+struct SelectPlainLoad {
+    const uint8_t* lbl; int64_t stride; int src_h, src_w; int64_t top, left;
+    __device__ __forceinline__ void operator()(int y, int x0, int n, unsigned (&d)[4]) const {
+        d[0] = d[1] = d[2] = d[3] = 0;
+        const int64_t sy = top + y, cs = left + x0;
+        if (sy < 0 || sy >= src_h || cs + n <= 0 || cs >= src_w) return;
+        const uint8_t* row = lbl + sy * stride;
+        if (n == SEL_SEG && cs >= 0 && cs + SEL_SEG <= src_w) {           // 16 bytes from any byte address: aligned dwords + v_alignbyte
+            const uintptr_t q = (uintptr_t)row + (uintptr_t)cs;
+            const uintptr_t qb = q & ~(uintptr_t)3, ql = (q + 15) & ~(uintptr_t)3;      // ql >= qb + 12
+            const unsigned sh = (unsigned)(q & 3);
+            const unsigned w0 = *(const unsigned*)qb, w1 = *(const unsigned*)(qb + 4), w2 = *(const unsigned*)(qb + 8),
+                           w3 = *(const unsigned*)(qb + 12);
+            const unsigned w4 = *(const unsigned*)(qb + 16 <= ql ? qb + 16 : ql);         // never past the dword of the last byte
+            d[0] = __builtin_amdgcn_alignbyte(w1, w0, sh); d[1] = __builtin_amdgcn_alignbyte(w2, w1, sh);
+            d[2] = __builtin_amdgcn_alignbyte(w3, w2, sh); d[3] = __builtin_amdgcn_alignbyte(w4, w3, sh);
+        } else {
+#pragma unroll
+            for (int k = 0; k < SEL_SEG; ++k) {
+                const int64_t sx = cs + k;
+                const bool in = k < n && sx >= 0 && sx < src_w;
+                const unsigned v = row[in ? sx : 0];                      // (cs + n > 0 and cs < src_w: column 0 exists)
+                d[k >> 2] |= (in ? v : 0u) << (8 * (k & 3));
+            }
+        }
+    }
+};
+
+// scaled stack: window pixel (y, x) is the NEAREST-resized label at resized (top + y, left + x) = lbl[ny[y]][nx[x]]; a table entry
+// of -1 says that the row / column lies outside the resized image, where the pad fill stands
+struct SelectScaledLoad {
+    const uint8_t* lbl; int64_t stride; const int *nx, *ny; unsigned fill;
+    __device__ __forceinline__ void operator()(int y, int x0, int n, unsigned (&d)[4]) const {
+        d[0] = d[1] = d[2] = d[3] = 0;
+        const int sy = ny[y];
+        const uint8_t* row = lbl + (int64_t)(sy < 0 ? 0 : sy) * stride;
+#pragma unroll
+        for (int k = 0; k < SEL_SEG; ++k) {
+            const int sx = k < n ? nx[x0 + k] : -1;
+            const bool in = sy >= 0 && sx >= 0;
+            const unsigned v = row[in ? sx : 0];
+            d[k >> 2] |= (k < n ? (in ? v : fill) : 0u) << (8 * (k & 3));
+        }
+    }
+};
+
+__device__ __forceinline__ void select_init(SelectShared& sh, const int64_t* __restrict__ lut) {
+    for (int i = threadIdx.x; i < SEL_WAVES * 256; i += SEL_THREADS) (&sh.hist[0][0])[i] = 0;
+    if (threadIdx.x < 256) sh.cls[threadIdx.x] = lut ? (long long)lut[threadIdx.x] : (long long)threadIdx.x;
+    __syncthreads();
+}
+
+// The verdict of the window just counted, the same value in every thread; leaves the counters zeroed for the next window.
+__device__ __forceinline__ bool select_passes(SelectShared& sh, long long ignore_class, double max_ratio) {
+    const int t = threadIdx.x;
+    __syncthreads();
+    if (t < 256) {
+        unsigned n = 0;
+#pragma unroll
+        for (int w = 0; w < SEL_WAVES; ++w) n += sh.hist[w][t];
+        sh.raw[t] = n;
+    }
+    if (t == 0) { sh.ncls = 0; sh.maxc = 0; sh.sum = 0; }
+    __syncthreads();
+    if (t < 256 && sh.raw[t] != 0 && sh.cls[t] != ignore_class) {
+        // the class of raw value t is counted by the FIRST raw value present in the window that the table maps to it
+        const long long c = sh.cls[t];
+        unsigned tot = 0;
+        bool rep = true;
+        for (int u = 0; u < 256; ++u)
+            if (sh.cls[u] == c) {
+                if (u < t && sh.raw[u] != 0) rep = false;
+                tot += sh.raw[u];
+            }
+        if (rep) { atomicAdd(&sh.ncls, 1u); atomicMax(&sh.maxc, tot); atomicAdd(&sh.sum, tot); }
+    }
+    for (int i = t; i < SEL_WAVES * 256; i += SEL_THREADS) (&sh.hist[0][0])[i] = 0;
+    __syncthreads();
+    // numpy's np.max(cnt) / np.sum(cnt) < cat_max_ratio: int64 / int64 is a float64 division; no division without two classes
+    return sh.ncls >= 2u && (double)sh.maxc / (double)sh.sum < max_ratio;
+}
+
+__global__ void __launch_bounds__(SEL_THREADS) input_crop_select_kernel(segf_input_sample* samples, const int32_t* __restrict__ cand,
+                                                                        int K, int H, int W, double max_ratio,
+                                                                        const int64_t* __restrict__ lut, long long ignore_class,
+                                                                        int32_t* __restrict__ chosen) {
+    __shared__ SelectShared sh;
+    const int b = blockIdx.x;
+    const int32_t* cd = cand + (int64_t)b * K * 2;
+    int pick = K - 1;
+    if (K > 1) {
+        const segf_input_sample s = samples[b];
+        select_init(sh, lut);
+        for (int k = 0; k < K - 1; ++k) {
+            if (k > 0 && cd[2 * k] == cd[2 * k - 2] && cd[2 * k + 1] == cd[2 * k - 1]) continue;      // the window that has just failed
+            select_count(sh.hist[threadIdx.x >> 6], H, W, SelectPlainLoad{s.lbl, s.lbl_stride, s.src_h, s.src_w, cd[2 * k], cd[2 * k + 1]});
+            if (select_passes(sh, ignore_class, max_ratio)) { pick = k; break; }
+        }
+    }
+    if (threadIdx.x == 0) {
+        samples[b].top = cd[2 * pick];
+        samples[b].left = cd[2 * pick + 1];
+        if (chosen) chosen[b] = pick;
+    }
+}
+
+// nearest_at's wave-uniform part for a lane at resized index `r`: the index of the wave's lane 0 (never negative), so that only the
+// last < 64 additions of the chain are counted per lane, as input_scale_tables_kernel keeps them under 256
+__device__ __forceinline__ int select_chain_base(int r) {
+    const int r0 = __builtin_amdgcn_readfirstlane(r - (int)(threadIdx.x & 63));
+    return r0 < 0 ? 0 : r0;
+}
+
+// the scaled stack's form: the nearest-index tables of a candidate's W columns and H rows go where input_scale_tables_kernel will put
+// those of the chosen window afterwards (the same chain of double additions, nearest_at), then the window is counted through them
+__global__ void __launch_bounds__(SEL_THREADS) input_scale_select_kernel(int H, int W, int kmax, ScaledWs t, const int32_t* __restrict__ cand,
+                                                                         int K, double max_ratio, const int64_t* __restrict__ lut,
+                                                                         long long ignore_class, int32_t* __restrict__ chosen) {
+    __shared__ SelectShared sh;
+    const int b = blockIdx.x;
+    const int32_t* cd = cand + (int64_t)b * K * 2;
+    int pick = K - 1;
+    if (K > 1) {
+        const segf_input_scaled_sample s = t.srecs[b];
+        const ScaledTabs tb = scaled_tabs(t, b, H, W, kmax);
+        select_init(sh, lut);
+        for (int k = 0; k < K - 1; ++k) {
+            const int top = cd[2 * k], left = cd[2 * k + 1];
+            if (k > 0 && top == cd[2 * k - 2] && left == cd[2 * k - 1]) continue;
+            for (int g = threadIdx.x; g < W; g += SEL_THREADS) {
+                const int rx = left + g;
+                tb.nx[g] = rx >= 0 && rx < s.res_w ? nearest_at(s.src_w, s.res_w, rx, select_chain_base(left + g)) : -1;
+            }
+            for (int g = threadIdx.x; g < H; g += SEL_THREADS) {
+                const int ry = top + g;
+                tb.ny[g] = ry >= 0 && ry < s.res_h ? nearest_at(s.src_h, s.res_h, ry, select_chain_base(top + g)) : -1;
+            }
+            __syncthreads();                                              // the tables are read by the whole workgroup
+            select_count(sh.hist[threadIdx.x >> 6], H, W, SelectScaledLoad{s.lbl, s.lbl_stride, tb.nx, tb.ny, (unsigned)(s.label_fill & 255)});
+            if (select_passes(sh, ignore_class, max_ratio)) { pick = k; break; }
+        }
+    }
+    if (threadIdx.x == 0) {
+        t.srecs[b].top = cd[2 * pick];
+        t.srecs[b].left = cd[2 * pick + 1];
+        if (chosen) chosen[b] = pick;
+    }
+}
+
+inline bool select_args_ok(int K, double max_ratio) { return K >= 1 && K <= 32 && max_ratio > 0.0 && max_ratio <= 1.0; }   // NaN fails
+
 // the launches of segf_input_train (arguments already checked): zero the luma sums, sum, transform
 int launch_input_train(const segf_input_sample* samples, int B, int H, int W, uint64_t* lsum_ws, const float* mean3, const float* std3,
                        const int64_t* label_lut, float* out_img, int64_t* out_lbl, void* stream) {
@@ -491,10 +708,11 @@ extern "C" int64_t segf_input_train_scaled_ws(int B, int H, int W, int kmax) {
     return scaled_ws(nullptr, B, H, W, kmax, nullptr);
 }
 
-extern "C" int segf_input_train_scaled(const segf_input_scaled_sample* samples, int B, int H, int W, int kmax, void* ws,
-                                       const float* mean3, const float* std3, const int64_t* label_lut, float* out_img,
-                                       int64_t* out_lbl, void* stream) {
-    if (B <= 0 || H <= 0 || W <= 0) return 0;
+namespace {
+
+// what segf_input_train_scaled refuses (include/segfac.h); 0 when the arguments stand
+int check_scaled(const segf_input_scaled_sample* samples, int B, int H, int W, int kmax, const void* ws, const float* mean3,
+                 const float* std3, const float* out_img, const int64_t* out_lbl) {
     if (!samples || !ws || !mean3 || !std3 || !out_img || !out_lbl) return SEGF_ERR_SHAPE;
     if ((int64_t)H * W > (int64_t)1 << 30 || kmax < 3 || B > 65535) return SEGF_ERR_SHAPE;
     if (((uintptr_t)out_img | (uintptr_t)out_lbl | (uintptr_t)ws) % 16 != 0) return SEGF_ERR_SHAPE;
@@ -507,14 +725,13 @@ extern "C" int segf_input_train_scaled(const segf_input_scaled_sample* samples, 
         if (s.top > big || s.top < -big || s.left > big || s.left < -big) return SEGF_ERR_SHAPE;
         if (resample_ksize(s.src_h, s.res_h) > kmax || resample_ksize(s.src_w, s.res_w) > kmax) return SEGF_ERR_SHAPE;
     }
+    return 0;
+}
+
+// the kernels of segf_input_train_scaled over records that already stand in ws
+int launch_scaled(const ScaledWs& t, int B, int H, int W, int kmax, const float* mean3, const float* std3, const int64_t* label_lut,
+                  float* out_img, int64_t* out_lbl, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    ScaledWs t;
-    scaled_ws(ws, B, H, W, kmax, &t);
-    if (!segf_trace().dry) {
-        hipError_t e = hipMemcpyAsync(t.srecs, samples, (size_t)B * sizeof(segf_input_scaled_sample), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);                 // the caller's array is free again on return
-        if (e != hipSuccess) return (int)e;
-    }
     const bool px4 = W % 4 == 0;
     const int nt = W > H ? W : H;
     hipLaunchKernelGGL(input_scale_tables_kernel, dim3((int)cdiv64(nt, 256), B), dim3(256), 0, st, H, W, kmax, t);
@@ -523,6 +740,71 @@ extern "C" int segf_input_train_scaled(const segf_input_scaled_sample* samples, 
     else hipLaunchKernelGGL(input_scale_crop_kernel<1>, dim3(bx, B), dim3(256), 0, st, H, W, kmax, t);
     SEGF_CHECK_LAUNCH();
     return launch_input_train(t.recs, B, H, W, (uint64_t*)t.lsum, mean3, std3, label_lut, out_img, out_lbl, stream);
+}
+
+}  // namespace
+
+extern "C" int segf_input_train_scaled(const segf_input_scaled_sample* samples, int B, int H, int W, int kmax, void* ws,
+                                       const float* mean3, const float* std3, const int64_t* label_lut, float* out_img,
+                                       int64_t* out_lbl, void* stream) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    const int rc = check_scaled(samples, B, H, W, kmax, ws, mean3, std3, out_img, out_lbl);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    ScaledWs t;
+    scaled_ws(ws, B, H, W, kmax, &t);
+    if (!segf_trace().dry) {
+        hipError_t e = hipMemcpyAsync(t.srecs, samples, (size_t)B * sizeof(segf_input_scaled_sample), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);                 // the caller's array is free again on return
+        if (e != hipSuccess) return (int)e;
+    }
+    return launch_scaled(t, B, H, W, kmax, mean3, std3, label_lut, out_img, out_lbl, stream);
+}
+
+extern "C" int segf_input_crop_select(segf_input_sample* samples, const int32_t* cand, int B, int K, int H, int W, double max_ratio,
+                                      const int64_t* label_lut, int64_t ignore_class, int32_t* chosen, void* stream) {
+    if (!select_args_ok(K, max_ratio) || !samples || !cand) return SEGF_ERR_SHAPE;
+    if ((int64_t)H * W > (int64_t)1 << 30 || (uintptr_t)samples % 16 != 0 || (uintptr_t)cand % 4 != 0) return SEGF_ERR_SHAPE;
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    hipLaunchKernelGGL(input_crop_select_kernel, dim3(B), dim3(SEL_THREADS), 0, (hipStream_t)stream, samples, cand, K, H, W, max_ratio,
+                       label_lut, (long long)ignore_class, chosen);
+    SEGF_CHECK_LAUNCH();
+    return 0;
+}
+
+// the workspace of segf_input_train_scaled with the [B][K][2] candidates behind it
+extern "C" int64_t segf_input_train_scaled_select_ws(int B, int H, int W, int kmax, int K) {
+    const int64_t base = segf_input_train_scaled_ws(B, H, W, kmax);
+    if (base == 0 || K < 1 || K > 32) return 0;
+    return base + (((int64_t)B * K * 8 + 15) & ~(int64_t)15);
+}
+
+extern "C" int segf_input_train_scaled_select(const segf_input_scaled_sample* samples, const int32_t* cand, int K, double max_ratio,
+                                              int64_t ignore_class, int32_t* chosen, int B, int H, int W, int kmax, void* ws,
+                                              const float* mean3, const float* std3, const int64_t* label_lut, float* out_img,
+                                              int64_t* out_lbl, void* stream) {
+    if (!select_args_ok(K, max_ratio) || !cand) return SEGF_ERR_SHAPE;
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    const int rc = check_scaled(samples, B, H, W, kmax, ws, mean3, std3, out_img, out_lbl);
+    if (rc) return rc;
+    const int big = 1 << 30;
+    for (int64_t i = 0; i < (int64_t)B * K * 2; ++i)
+        if (cand[i] > big || cand[i] < -big) return SEGF_ERR_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    ScaledWs t;
+    const int64_t base = scaled_ws(ws, B, H, W, kmax, &t);
+    int32_t* dcand = (int32_t*)((uint8_t*)ws + base);
+    if (!segf_trace().dry) {
+        hipError_t e = hipMemcpyAsync(t.srecs, samples, (size_t)B * sizeof(segf_input_scaled_sample), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(dcand, cand, (size_t)B * K * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);                 // both host arrays are free again on return
+        if (e != hipSuccess) return (int)e;
+    }
+    // the selection first: the coefficient tables depend on the window it writes into the uploaded records
+    hipLaunchKernelGGL(input_scale_select_kernel, dim3(B), dim3(SEL_THREADS), 0, st, H, W, kmax, t, (const int32_t*)dcand, K, max_ratio,
+                       label_lut, (long long)ignore_class, chosen);
+    SEGF_CHECK_LAUNCH();
+    return launch_scaled(t, B, H, W, kmax, mean3, std3, label_lut, out_img, out_lbl, stream);
 }
 
 // ---- single-image inference (estimate_model.py:85-97): T.Resize((nH, nW)) on the uint8 CHW tensor + x / 255 + Normalize -----------

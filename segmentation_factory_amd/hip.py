@@ -22,7 +22,7 @@ _lib = None
 
 # ---- the binding is derived from include/segfac.h: its declarations are the only copy of the C ABI ----------------------------
 _i, _l, _f, _p = C.c_int, C.c_int64, C.c_float, C.c_void_p
-_SCALAR = {'int': _i, 'int32_t': _i, 'int64_t': _l, 'float': _f}
+_SCALAR = {'int': _i, 'int32_t': _i, 'int64_t': _l, 'float': _f, 'double': C.c_double}
 _POINTEE = {'void', 'char', 'int', 'int32_t', 'int64_t', 'uint8_t', 'uint64_t', 'float'}
 
 
@@ -1566,6 +1566,55 @@ def input_train_scaled(samples, B, H, W, kmax, mean3, std3, label_lut, out_img=N
     _chk_arg(lib().segf_input_train_scaled(C.cast(samples, C.c_void_p), B, H, W, kmax, _ptr(ws), _ptr(mean3), _ptr(std3),
                                            _ptr(label_lut), _ptr(out_img), _ptr(out_lbl), _stream()), 'segf_input_train_scaled')
     return out_img, out_lbl
+
+
+def input_crop_select(samples, cand, B, K, H, W, max_ratio, label_lut, ignore_class, chosen=None):
+    """segf_input_crop_select: the class-balanced choice among K candidate windows per sample (the rule: include/segfac.h).
+    `samples` as for `input_train` (top / left of the device records are rewritten in place), `cand` = int32 device tensor
+    [B, K, 2] of non-negative (top, left) -> `chosen`, int32 [B] on the device (nothing is read back).  ValueError when the library
+    refuses an argument."""
+    _need_cuda(samples, cand, label_lut, chosen)
+    assert samples.dtype == torch.uint8 and samples.numel() == B * C.sizeof(InputSample)
+    assert cand.dtype == torch.int32 and cand.is_contiguous() and cand.numel() == B * K * 2
+    assert label_lut is None or (label_lut.dtype == torch.int64 and label_lut.numel() == 256)
+    if chosen is None:
+        chosen = torch.empty(B, dtype=torch.int32, device=samples.device)
+    assert chosen.dtype == torch.int32 and chosen.is_contiguous() and chosen.numel() == B
+    _chk_arg(lib().segf_input_crop_select(_ptr(samples), _ptr(cand), B, K, H, W, float(max_ratio), _ptr(label_lut), int(ignore_class),
+                                          _ptr(chosen), _stream()), 'segf_input_crop_select')
+    return chosen
+
+
+def input_train_scaled_select(samples, cand, B, K, H, W, kmax, max_ratio, ignore_class, mean3, std3, label_lut, out_img=None,
+                              out_lbl=None, ws=None, chosen=None):
+    """segf_input_train_scaled_select: `input_train_scaled` with the class-balanced choice among K candidate windows per sample in
+    front (the rule: include/segfac.h).  `cand` = a HOST ctypes c_int32 array of B * K * 2 values, (top, left) in resized
+    coordinates -> (fp32 [B, 3, H, W], int64 [B, H, W], chosen int32 [B] on the device).  ``ws``: a uint8 device tensor of
+    segf_input_train_scaled_select_ws(B, H, W, kmax, K) bytes (default: allocated here)."""
+    _need_cuda(mean3, std3, label_lut, out_img, out_lbl, ws, chosen)
+    assert isinstance(samples, C.Array) and samples._type_ is InputScaledSample and len(samples) == B
+    assert isinstance(cand, C.Array) and cand._type_ is C.c_int32 and len(cand) == B * K * 2
+    assert mean3.dtype == torch.float32 and std3.dtype == torch.float32 and mean3.numel() == 3 and std3.numel() == 3
+    assert label_lut is None or (label_lut.dtype == torch.int64 and label_lut.numel() == 256)
+    dev = mean3.device
+    if out_img is None:
+        out_img = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+    if out_lbl is None:
+        out_lbl = torch.empty((B, H, W), dtype=torch.int64, device=dev)
+    if chosen is None:
+        chosen = torch.empty(B, dtype=torch.int32, device=dev)
+    assert out_img.is_contiguous() and out_lbl.is_contiguous() and out_img.numel() == B * 3 * H * W and out_lbl.numel() == B * H * W
+    assert out_img.dtype == torch.float32 and out_lbl.dtype == torch.int64
+    assert chosen.dtype == torch.int32 and chosen.is_contiguous() and chosen.numel() == B
+    need = int(lib().segf_input_train_scaled_select_ws(B, H, W, kmax, K))
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need
+    _chk_arg(lib().segf_input_train_scaled_select(C.cast(samples, C.c_void_p), C.cast(cand, C.c_void_p), K, float(max_ratio),
+                                                  int(ignore_class), _ptr(chosen), B, H, W, kmax, _ptr(ws), _ptr(mean3), _ptr(std3),
+                                                  _ptr(label_lut), _ptr(out_img), _ptr(out_lbl), _stream()),
+             'segf_input_train_scaled_select')
+    return out_img, out_lbl, chosen
 
 
 def input_val(img, lbl, out_h, out_w, mean3, std3, label_lut):

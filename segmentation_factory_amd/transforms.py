@@ -18,7 +18,14 @@ what the reference's single-process loader yields.  No CPU fallback: the tensors
 Scale augmentation (``DeviceTrainTransform(scale_range=, pad_if_needed=, label_fill=)``): ExtRandomScale (extra_transform.py:75-96)
 and ExtRandomCrop(pad_if_needed=True) (:378-385) in front of the same stack, `segf_input_train_scaled` -- Pillow's resize evaluated
 for the crop window only.
+
+Class-balanced crop choice (``DeviceTrainTransform(cat_max_ratio=, crop_tries=, ignore_class=)``): mmsegmentation's
+RandomCrop(crop_size, cat_max_ratio) in front of either stack.  The host draws ``crop_tries + 1`` candidate windows where it drew
+one; which of them is used is decided on the device from the label histogram of each window (`segf_input_crop_select`,
+`segf_input_train_scaled_select`; the rule is written out in include/segfac.h), because the labels live in HBM and a verdict read
+back to the host would make the loader wait for the train step still in flight.
 """
+import ctypes as C
 import random as _random
 
 import torch
@@ -80,10 +87,17 @@ class DeviceTrainTransform(_Base):
     (extra_transform.py:75-96, 319-392): `draw_scaled` makes the draws and the size arithmetic, `segf_input_train_scaled` computes
     the crop window of the resized image without ever forming that image.  ``label_fill``: the raw uint8 label value of the
     border that ``pad_if_needed`` adds (the reference's F.pad fills 0; a training run wants its ignore label there).  Without
-    ``scale_range`` and ``pad_if_needed`` nothing changes."""
+    ``scale_range`` and ``pad_if_needed`` nothing changes.
+
+    With ``cat_max_ratio=R`` (0 < R < 1) the crop is mmseg's RandomCrop(size, cat_max_ratio=R): ``crop_tries + 1`` windows are drawn
+    where one was (consecutive (row, column) pairs on the same stream, before the jitter factors), and the device takes the first
+    of the first ``crop_tries`` in which no class covers R or more of the pixels whose class is not ``ignore_class`` and at least two
+    classes occur, else the last one untested.  `last_chosen` is the device int32 [B] index of the window each sample of the last
+    call took (0 for a sample that had one window only).  With ``cat_max_ratio`` None or >= 1 nothing changes."""
 
     def __init__(self, image_size, brightness=0.5, contrast=0.5, saturation=0.5, flip_p=0.5, mean=IMAGENET_MEAN, std=IMAGENET_STD,
-                 label_lut=None, device='cuda', rng=None, scale_range=None, pad_if_needed=False, label_fill=0):
+                 label_lut=None, device='cuda', rng=None, scale_range=None, pad_if_needed=False, label_fill=0, cat_max_ratio=None,
+                 crop_tries=10, ignore_class=255):
         super().__init__(mean, std, label_lut, device)
         self.size = (int(image_size), int(image_size)) if isinstance(image_size, (int, float)) else tuple(int(v) for v in image_size)
         self.ranges = [(OP_BRIGHTNESS, _jitter_range(brightness)), (OP_CONTRAST, _jitter_range(contrast)),
@@ -98,6 +112,14 @@ class DeviceTrainTransform(_Base):
             raise ValueError(f'label_fill {label_fill} is not a uint8 label value')
         self.scale_range, self.pad_if_needed, self.label_fill = scale_range, bool(pad_if_needed), int(label_fill)
         self.scaled = scale_range is not None or self.pad_if_needed
+        if cat_max_ratio is not None and not cat_max_ratio > 0:
+            raise ValueError(f'cat_max_ratio {cat_max_ratio} should be in (0, 1]')
+        if not 1 <= int(crop_tries) <= 31:
+            raise ValueError(f'crop_tries {crop_tries} should be 1 .. 31')
+        self.balanced = cat_max_ratio is not None and cat_max_ratio < 1          # mmseg: `if self.cat_max_ratio < 1.`
+        self.cat_max_ratio = float(cat_max_ratio) if self.balanced else None
+        self.crop_tries, self.ignore_class = int(crop_tries), int(ignore_class)
+        self.last_chosen = None
 
     def _jitter_flip(self):
         ops = [(op, self.rng.uniform(r[0], r[1])) for op, r in self.ranges if r is not None]
@@ -116,6 +138,19 @@ class DeviceTrainTransform(_Base):
         ops, flip = self._jitter_flip()
         return top, left, ops, flip
 
+    def _windows(self, h, w):
+        """The crop_tries + 1 candidate origins in an h x w image, (row, column) pairs drawn consecutively."""
+        th, tw = self.size
+        return [(self.rng.randint(0, abs(h - th)), self.rng.randint(0, abs(w - tw))) for _ in range(self.crop_tries + 1)]
+
+    def draw_balanced(self, src_h, src_w):
+        """`draw` for the class-balanced crop: -> (windows, [(op, factor), ...], flip) with windows = the crop_tries + 1 candidate
+        (top, left) in drawing order, or the single (0, 0) when the source already has the crop's size (nothing is drawn then)."""
+        th, tw = self.size
+        windows = [(0, 0)] if src_w == tw and src_h == th else self._windows(src_h, src_w)
+        ops, flip = self._jitter_flip()
+        return windows, ops, flip
+
     @staticmethod
     def pad_border(res_h, res_w, th, tw):
         """ExtRandomCrop.__call__ with pad_if_needed (extra_transform.py:378-385): F.pad with an int pads ALL FOUR borders, first
@@ -131,7 +166,8 @@ class DeviceTrainTransform(_Base):
         """One sample's random values for the scaled stack, in the reference's order on the `random` stream: scale (:90), crop
         row, crop column (:359-360; none when the padded size equals the crop), the jitter factors, the shuffle, the flip.
         -> dict(scale, res_h, res_w, P, top, left, ops, flip, label_fill); (top, left) is the crop origin in the RESIZED image's
-        coordinates (crop origin in the padded image minus P) and may be negative."""
+        coordinates (crop origin in the padded image minus P) and may be negative.  With ``cat_max_ratio`` the dict also has
+        `windows`, the crop_tries + 1 candidate origins in drawing order (one when nothing is drawn), and (top, left) is the first."""
         th, tw = self.size
         scale = self.rng.uniform(self.scale_range[0], self.scale_range[1]) if self.scale_range is not None else None
         res_h, res_w = (src_h, src_w) if scale is None else (int(src_h * scale), int(src_w * scale))      # :91
@@ -139,15 +175,22 @@ class DeviceTrainTransform(_Base):
             raise ValueError(f'scale {scale} leaves nothing of a {src_h} x {src_w} image')
         P = self.pad_border(res_h, res_w, th, tw) if self.pad_if_needed else 0
         hp, wp = res_h + 2 * P, res_w + 2 * P
+        windows = None
         if wp == tw and hp == th:
             i, j = 0, 0
+        elif self.balanced:
+            windows = self._windows(hp, wp)
+            i, j = windows[0]
         else:
             i = self.rng.randint(0, abs(hp - th))
             j = self.rng.randint(0, abs(wp - tw))
         ops, flip = self._jitter_flip()
         # without pad_if_needed a crop that hangs over the edge reads 0 in the label too (Image.crop)
-        return dict(scale=scale, res_h=res_h, res_w=res_w, P=P, top=i - P, left=j - P, ops=ops, flip=flip,
-                    label_fill=self.label_fill if self.pad_if_needed else 0)
+        p = dict(scale=scale, res_h=res_h, res_w=res_w, P=P, top=i - P, left=j - P, ops=ops, flip=flip,
+                 label_fill=self.label_fill if self.pad_if_needed else 0)
+        if self.balanced:
+            p['windows'] = [(a - P, b - P) for a, b in windows] if windows is not None else [(i - P, j - P)]
+        return p
 
     def pack_scaled(self, images, labels, params):
         """-> (host array of segf_input_scaled_sample records, the largest tap count among them)."""
@@ -169,7 +212,22 @@ class DeviceTrainTransform(_Base):
                 kmax = max(kmax, hip.resample_ksize(r.src_h, r.res_h), hip.resample_ksize(r.src_w, r.res_w))
         return recs, kmax
 
-    def pack(self, images, labels, params):
+    def _candidates(self, windows):
+        """Per-sample window lists -> (K, flat [B][K][2] int32 values); K = 1 when no sample has a choice, else crop_tries + 1 (a
+        sample without a choice repeats its window: the kernel tests a repeated window once)."""
+        K = max(len(w) for w in windows)
+        if K > 1 and any(len(w) not in (1, K) for w in windows):
+            raise ValueError('every sample needs one window or the same number of candidate windows')
+        return K, [int(v) for w in windows for win in (w if len(w) == K else list(w) * K) for v in win]
+
+    def _single_to_zero(self, windows, K):
+        """A sample without a choice in a batch that has one: its repeated window is index 0, whatever the test said of it."""
+        if any(len(w) != K for w in windows):
+            keep = torch.tensor([int(len(w) == K) for w in windows], dtype=torch.int32).to(self.device)
+            self.last_chosen.mul_(keep)                      # on the device: nothing is read back
+
+    def pack(self, images, labels, params, cand=None):
+        """-> the device records; with `cand` (flat [B][K][2] values) -> (records, int32 candidates) from ONE upload."""
         recs = (hip.InputSample * len(images))()
         for k, (img, lbl, (top, left, ops, flip)) in enumerate(zip(images, labels, params)):
             self._check(img, lbl)
@@ -183,25 +241,56 @@ class DeviceTrainTransform(_Base):
                 order |= op << (2 * j)
                 r.factor[j] = f                              # Python float -> C float, as Image.blend's (float)alpha
             r.order = order
-        host = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8)
-        return host.to(self.device, non_blocking=False)
+        if cand is None:
+            host = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8)
+            return host.to(self.device, non_blocking=False)
+        # the library cannot refuse these: the candidates of segf_input_crop_select stand on the device and are not read on the host
+        if min(cand) < 0 or max(cand) > 1 << 30:
+            raise ValueError('candidate windows of the unscaled stack must start inside [0, 2^30]')
+        nrec = C.sizeof(recs)                                # a multiple of 8: the int32 candidates stand aligned behind the records
+        dev = torch.frombuffer(bytearray(bytes(recs) + bytes((C.c_int32 * len(cand))(*cand))), dtype=torch.uint8).to(self.device)
+        return dev[:nrec], dev[nrec:].view(torch.int32)
 
     def __call__(self, images, labels, params=None, out=None):
         """images: list of uint8 [h, w, 3] device tensors, labels: list of uint8 [h, w] -> (fp32 [B, 3, S, S], int64 [B, S, S]).
-        ``params`` overrides the draws (one (top, left, ops, flip) per sample); ``out`` = (image, label) tensors to fill in place
+        ``params`` overrides the draws (one (top, left, ops, flip) per sample; with ``cat_max_ratio`` `draw_balanced`'s (windows, ops,
+        flip) as well, and a sample given ONE window takes it without a test); ``out`` = (image, label) tensors to fill in place
         (e.g. the input buffers of a captured train step: zero-copy feed).  With ``scale_range`` / ``pad_if_needed`` the draws
         are `draw_scaled`'s dicts and the batch comes from `segf_input_train_scaled`."""
         oi, ol = out if out is not None else (None, None)
+        B, (H, W) = len(images), self.size
         if self.scaled:
             if params is None:
                 params = [self.draw_scaled(int(i.shape[0]), int(i.shape[1])) for i in images]
+            wins = [p.get('windows') or [(p['top'], p['left'])] for p in params]
+            K, cand = self._candidates(wins) if self.balanced else (1, None)
             recs, kmax = self.pack_scaled(images, labels, params)
-            return hip.input_train_scaled(recs, len(images), self.size[0], self.size[1], kmax, self.mean, self.std, self.label_lut,
-                                          oi, ol)
+            if K == 1:
+                self.last_chosen = torch.zeros(B, dtype=torch.int32, device=self.device) if self.balanced else None
+                return hip.input_train_scaled(recs, B, H, W, kmax, self.mean, self.std, self.label_lut, oi, ol)
+            img, lbl, self.last_chosen = hip.input_train_scaled_select(
+                recs, (C.c_int32 * len(cand))(*cand), B, K, H, W, kmax, self.cat_max_ratio, self.ignore_class, self.mean, self.std,
+                self.label_lut, oi, ol)
+            self._single_to_zero(wins, K)
+            return img, lbl
+        if not self.balanced:
+            if params is None:
+                params = [self.draw(int(i.shape[0]), int(i.shape[1])) for i in images]
+            samples = self.pack(images, labels, params)
+            return hip.input_train(samples, B, H, W, self.mean, self.std, self.label_lut, oi, ol)
         if params is None:
-            params = [self.draw(int(i.shape[0]), int(i.shape[1])) for i in images]
-        samples = self.pack(images, labels, params)
-        return hip.input_train(samples, len(images), self.size[0], self.size[1], self.mean, self.std, self.label_lut, oi, ol)
+            params = [self.draw_balanced(int(i.shape[0]), int(i.shape[1])) for i in images]
+        # `draw_balanced`'s (windows, ops, flip), or `draw`'s (top, left, ops, flip): a window without a choice
+        params = [p if len(p) == 3 else ([(p[0], p[1])], p[2], p[3]) for p in params]
+        K, cand = self._candidates([p[0] for p in params])
+        first = [(p[0][0][0], p[0][0][1], p[1], p[2]) for p in params]
+        if K == 1:
+            self.last_chosen = torch.zeros(B, dtype=torch.int32, device=self.device)
+            return hip.input_train(self.pack(images, labels, first), B, H, W, self.mean, self.std, self.label_lut, oi, ol)
+        samples, dcand = self.pack(images, labels, first, cand)
+        self.last_chosen = hip.input_crop_select(samples, dcand, B, K, H, W, self.cat_max_ratio, self.label_lut, self.ignore_class)
+        self._single_to_zero([p[0] for p in params], K)
+        return hip.input_train(samples, B, H, W, self.mean, self.std, self.label_lut, oi, ol)
 
 
 class DeviceValTransform(_Base):

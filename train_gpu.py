@@ -171,11 +171,35 @@ def get_args_parser():
     parser.add_argument('--aug-pad-label', dest='aug_pad_label', type=int, default=None,
                         help='--aug-scale: raw label value of the padded border (default: --ignore_label, so that padding does not '
                              'train as class 0)')
+    parser.add_argument('--aug-cat-max-ratio', dest='aug_cat_max_ratio', type=float, default=None, metavar='R',
+                        help='--device-input: class-balanced crop choice, mmsegmentation\'s RandomCrop(cat_max_ratio=R): a crop window '
+                             'in which one class covers R or more of the pixels that are not --ignore_label, or which holds fewer '
+                             'than two classes, is drawn again (0 < R <= 1; 1 = off, as in mmseg); works with and without --aug-scale')
+    parser.add_argument('--aug-crop-tries', dest='aug_crop_tries', type=int, default=None, metavar='N',
+                        help='--aug-cat-max-ratio: windows that are tested before the next draw is taken untested (default 10; 1 .. 31)')
     return parser
 
 
+def check_balanced_args(args):
+    if args.aug_cat_max_ratio is None:
+        if args.aug_crop_tries is not None:
+            raise SystemExit('--aug-crop-tries needs --aug-cat-max-ratio')
+        return
+    if not args.device_input:
+        raise SystemExit('--aug-cat-max-ratio needs --device-input: without it the batches come from the dataset classes of the '
+                         'reference, which apply their own transform stack')
+    if not 0 < args.aug_cat_max_ratio <= 1:
+        raise SystemExit(f'--aug-cat-max-ratio {args.aug_cat_max_ratio}: expected 0 < R <= 1')
+    if args.aug_crop_tries is None:
+        args.aug_crop_tries = 10
+    if not 1 <= args.aug_crop_tries <= 31:
+        raise SystemExit(f'--aug-crop-tries {args.aug_crop_tries}: expected 1 <= N <= 31')
+
+
 def check_aug_args(args):
-    """--aug-scale belongs to the device input pipeline: the DataLoader path runs the reference's own dataset transforms."""
+    """--aug-scale and --aug-cat-max-ratio belong to the device input pipeline: the DataLoader path runs the reference's own dataset
+    transforms."""
+    check_balanced_args(args)
     if args.aug_scale is None:
         if args.aug_pad_label is not None:
             raise SystemExit('--aug-pad-label needs --aug-scale')
@@ -257,11 +281,14 @@ def build_device_loader(args, train_set):
                 assert int(lbl.min()) >= 0 and int(lbl.max()) <= 255, 'label values must fit uint8 (255 = ignore)'
                 lbl = lbl.to(torch.uint8)
             ds.add(torch.as_tensor(np.asarray(img)), lbl)
+    kw = {}
+    if args.aug_cat_max_ratio is not None:
+        kw = dict(cat_max_ratio=args.aug_cat_max_ratio, crop_tries=args.aug_crop_tries, ignore_class=args.ignore_label)
     if args.aug_scale is not None:
         tf = DeviceTrainTransform(args.image_size, device=args.device, scale_range=tuple(args.aug_scale), pad_if_needed=True,
-                                  label_fill=args.aug_pad_label)
+                                  label_fill=args.aug_pad_label, **kw)
     else:
-        tf = DeviceTrainTransform(args.image_size, device=args.device)
+        tf = DeviceTrainTransform(args.image_size, device=args.device, **kw)
     # seed 0 = the DistributedSampler of train_gpu.py:212-214 (constructed without a seed)
     return DeviceBatchLoader(ds, args.batch_size, tf, shuffle=True, seed=0, rank=utils.get_rank(), world=utils.get_world_size())
 
